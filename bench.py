@@ -13,12 +13,27 @@ step buckets each batch by (suite, key) on the device (qpp_plan_build)
 inside the timed region, once for the protect batch and once for the
 unprotect batch.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config ns] [--no-e2e]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config ns] [--dump-outputs DIR]
+    python bench.py --full [--no-e2e] [--cpu-seconds S] ...
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 
-After the timed region rank 0 also times the path the north star says
-starts and ends in host memory (UDP socket buffers): pinned H2D -> protect ->
-unprotect -> D2H on its own 1Mi-packet workload, reported as "e2e" beside
+A plain run does only what the headline figure needs: it builds the workload,
+warms up, times the K steps and prints the line (`value`, `ms_per_step`, the
+kernels' event times taken inside the timed steps).  --dump-outputs DIR also
+writes what the last timed step left in the caller's output buffers, as
+DIR/<name>.npy (see dump_outputs); the workload is seeded, so two builds run
+with the same arguments can be compared array for array.
+
+Everything else is behind --full (off by default): the CPU baselines before
+the GPU is touched, the sustained leg, the status and round-trip checks of the
+last step, the HBM copy probe of the roofline, the key-schedule timing and the
+end-to-end legs; the knobs below that shape them (--cpu-seconds, --no-e2e,
+--no-check, --sustain-seconds, ...) act only with --full, and the line carries
+null for whatever did not run.
+
+With --full, after the timed region rank 0 also times the path the north star
+says starts and ends in host memory (UDP socket buffers): pinned H2D -> protect
+-> unprotect -> D2H on its own 1Mi-packet workload, reported as "e2e" beside
 `value` and never as `value` (--no-e2e skips it).
 
 --gpus N without a launcher (WORLD_SIZE unset) starts N rank processes
@@ -73,6 +88,11 @@ def parse():
     ap.add_argument("--warmup", type=int, default=10,
                     help="untimed steps first (the GPU clock needs ~20 ms of work to ramp)")
     ap.add_argument("--config", default="ns", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: CPU baselines, the sustained leg, "
+                         "the checks of the last step, the HBM copy probe, key-schedule timing, end-to-end legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy")
     ap.add_argument("--packets", type=int, default=0, help="override packets per GPU")
     ap.add_argument("--order", choices=("grouped", "round_robin", "random"), default=None,
                     help="override the config's arrival order (non-grouped orders are bucketed)")
@@ -419,6 +439,50 @@ def key_schedule(eng_cls, n_keys, suite, version):
                     "host = HKDF only, 1 thread"}
 
 
+DUMP_PACKETS = 2048  # packets whose bytes --dump-outputs keeps (2 buffers x 2048 x 1200 float32 = 19.7 MB)
+DUMP_ALL_MAX = 1 << 21  # the per-packet arrays cover every packet up to this many (4 x 4 B each: 32 MiB)
+
+
+def dump_outputs(path, n, shift, d_wire, d_back, d_r1, d_r2):
+    """--dump-outputs: what the last timed step left in the buffers a caller
+    of protect / unprotect receives, as float32 / float64 .npy files under
+    `path` (under 64 MB in all):
+
+      sample_index            the DUMP_PACKETS packet slots kept byte for byte (a fixed, seeded choice)
+      protect_wire            [m, 1200] their wire bytes (header-protected header, ciphertext, tag)
+      unprotect_plain         [m, 1200] their slots of the unprotect output (header, plaintext, 16 spare)
+      protect_results,        [m, 4] their RESULT records: pn, status, hdr_len, out_len
+      unprotect_results
+      protect_wire_sums,      [n] the byte sum of every packet's slot in either buffer and
+      unprotect_plain_sums,   [n] every packet's status (n <= DUMP_ALL_MAX; else of the sampled
+      protect_status,             packets only), so that a difference in any packet shows
+      unprotect_status
+    """
+    import torch
+    from aioquic_amd import layout as L
+
+    os.makedirs(path, exist_ok=True)
+    m = min(n, DUMP_PACKETS)
+    sel = np.sort(np.random.default_rng(0xD0).choice(n, m, replace=False))
+    d_sel = torch.from_numpy(sel).to(d_wire.device)
+    span = n * 1200
+
+    def save(name, a, dtype=np.float32):
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=dtype))
+
+    save("sample_index", sel, np.float64)
+    every = n <= DUMP_ALL_MAX
+    for buf, res, bname, rname in ((d_wire, d_r1, "protect_wire", "protect"),
+                                   (d_back, d_r2, "unprotect_plain", "unprotect")):
+        slots = buf[shift:shift + span].view(n, 1200)
+        save(bname, slots[d_sel].cpu().numpy())
+        r = res.cpu().numpy().view(L.RESULT)
+        save(rname + "_results", np.stack([r[f][sel].astype(np.float64) for f in r.dtype.names], axis=1), np.float64)
+        sums = slots.sum(dim=1, dtype=torch.int32) if every else slots[d_sel].sum(dim=1, dtype=torch.int32)
+        save(bname + "_sums", sums.cpu().numpy())
+        save(rname + "_status", r["status"] if every else r["status"][sel])
+
+
 METRIC = "GiB/s device-resident AEAD protect+unprotect, 1200B packets, 1/2/4/8 MI355X"
 
 
@@ -514,7 +578,7 @@ def main():
     # rank 0 of an N = 1 run only (the same host and sample at every N; a
     # scaling run's line carries null)
     cpu = cpu_all = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         cpu = cpu_baseline(w, args.cpu_seconds, cfg, 1)
         if args.cpu_all_cores:
             cpu_all = cpu_baseline(w, max(2.0, args.cpu_seconds / 2), cfg, cpu_share())
@@ -605,12 +669,16 @@ def main():
     hev_flags = hev.flags
     hev.close()
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, f"rank{rank}"),
+                     n, w.wire_size - n * 1200, d_wire, d_back, d_r1, d_r2)
+
     # sustained: the same step back to back for a few seconds after the timed
     # region, no events (the clocks' steady state; reported beside `value`,
     # never as it); its last step's results are checked below like the
     # timed region's
     sustained = None
-    if world == 1 and args.sustain_seconds > 0:
+    if args.full and world == 1 and args.sustain_seconds > 0:
         k_s = max(1, int(args.sustain_seconds / max(elapsed / args.steps, 1e-6)))
         torch.cuda.synchronize(dev)
         t_s = time.perf_counter()
@@ -623,13 +691,15 @@ def main():
                      "ms_per_step": round(dt_s / k_s * 1e3, 4),
                      "note": "the timed region's step repeated back to back after it, without timing events"}
 
-    # after timing: every packet of the last step authenticated, and (unless
-    # --no-check) the unprotected bytes equal the plaintext, every byte
-    r1 = d_r1.cpu().numpy().view(L.RESULT)
-    r2 = d_r2.cpu().numpy().view(L.RESULT)
-    tags_ok = bool((r1["status"] == 0).all() and (r2["status"] == 0).all())
-    rt_ok = bool(torch.equal(d_back, d_plain)) if args.check else None
-    ok = tags_ok and rt_ok is not False
+    # --full, after timing: every packet of the last step authenticated, and
+    # (unless --no-check) the unprotected bytes equal the plaintext, every byte
+    tags_ok = rt_ok = ok = None
+    if args.full:
+        r1 = d_r1.cpu().numpy().view(L.RESULT)
+        r2 = d_r2.cpu().numpy().view(L.RESULT)
+        tags_ok = bool((r1["status"] == 0).all() and (r2["status"] == 0).all())
+        rt_ok = bool(torch.equal(d_back, d_plain)) if args.check else None
+        ok = tags_ok and rt_ok is not False
     mine = {"rank": rank, "device": local, "packets": n, "status_ok": ok, "tags_ok": tags_ok,
             "round_trip_ok": rt_ok, "seconds": round(float(elapsed_own), 6),
             "kernels_ms": {"protect": round(t_prot * 1e3, 4), "unprotect": round(t_unp * 1e3, 4)}}
@@ -637,11 +707,11 @@ def main():
     if world > 1:
         per_rank = [None] * world
         dist.all_gather_object(per_rank, mine)
-    ok = all(r["status_ok"] for r in per_rank)
+    ok = all(r["status_ok"] for r in per_rank) if args.full else None
 
     total_bytes = float(n) * 1200 * args.steps * world
     value = total_bytes / elapsed / GIB
-    copy_gbs = hbm_copy_gbs(dev) if rank == 0 else None
+    copy_gbs = hbm_copy_gbs(dev) if args.full and rank == 0 else None
     kern_t = max(t_prot, t_unp)
     dom = "protect" if t_prot >= t_unp else "unprotect"
     achieved = BYTES_PER_PKT_KERNEL * n / kern_t / 1e9
@@ -663,6 +733,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": bool(args.full),
             "ms_per_step": round(elapsed / args.steps * 1e3, 4),
             "higher_is_better": True,
             "scaling": "weak",
@@ -691,14 +762,15 @@ def main():
             "cpu_baseline_all_cores": cpu_all,
             "sustained": sustained,
             "status_ok": ok,
-            "round_trip_checked": bool(args.check),
+            "round_trip_checked": bool(args.full and args.check),
+            "outputs_dumped": args.dump_outputs,
             "ranks": per_rank,
             "devices_visible": torch.cuda.device_count(),
             "rehearsal_shared_devices": world > torch.cuda.device_count(),
         }
-        if w.n_keys >= 64:
+        if args.full and w.n_keys >= 64:
             out["key_schedule"] = key_schedule(PacketEngine, w.n_keys, cfg["suite"], cfg["version"])
-        if args.e2e:
+        if args.full and args.e2e:
             # the PCIe legs start from a clean host and device: the timed
             # region's buffers go first (host and device memory they held
             # otherwise sits beside the legs' own multi-GiB buffers)
