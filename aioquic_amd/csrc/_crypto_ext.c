@@ -1837,6 +1837,19 @@ static PyObject *py_source_hash(PyObject *m, PyObject *unused)
     return PyUnicode_FromString(kSourceHash + 16);
 }
 
+/* test hook: the receive walks' decode_pn_signed as it stands (tests/test_pn_decode.py) */
+static PyObject *py_decode_pn_signed(PyObject *m, PyObject *args)
+{
+    unsigned long long pn, expected;
+    int pn_len;
+    if (!PyArg_ParseTuple(args, "KiK", &pn, &pn_len, &expected)) return NULL;
+    if (pn_len < 1 || pn_len > 4) {
+        PyErr_SetString(PyExc_ValueError, "pn_len must be 1..4");
+        return NULL;
+    }
+    return PyLong_FromLongLong(decode_pn_signed(pn, pn_len, expected));
+}
+
 static PyMethodDef module_methods[] = {
     {"protect", py_protect, METH_VARARGS, "protect(table, desc_ptr, n, in_ptr, out_ptr, res_ptr, stream, plan=None)"},
     {"unprotect", py_unprotect, METH_VARARGS, "unprotect(table, desc_ptr, n, in_ptr, out_ptr, res_ptr, stream, plan=None)"},
@@ -1863,6 +1876,8 @@ static PyMethodDef module_methods[] = {
     {"abi_version", py_abi, METH_NOARGS, "C ABI version of libquicpp"},
     {"watchdog_count", py_watchdog, METH_NOARGS, "GCM table-entry watchdog events on the current device (0 expected)"},
     {"source_hash", py_source_hash, METH_NOARGS, "hash of the native sources this module was built from"},
+    {"_decode_pn_signed", py_decode_pn_signed, METH_VARARGS,
+     "_decode_pn_signed(pn, pn_len, expected) -> the walks' decode of pn's low pn_len bytes (-1: negative); test hook"},
     {NULL},
 };
 

@@ -412,12 +412,29 @@ __device__ __forceinline__ void wipe_payload(const Pkt &P, int sub, OWN own)
 // above kOob are out of range: loads return zeros, stores are dropped.  This
 // lets every step issue exactly one load and one store per lane with no
 // branch around them, so the compiler can count vmcnt instead of draining.
-constexpr uint32_t kBufBytes = 0xffffff00u;
+constexpr uint32_t kBufBytes = QPP_ITEM_SPAN_MAX;
 constexpr uint32_t kOob = 0xfffffff0u;
+static_assert(kBufBytes < kOob, "the out-of-range offset must lie past the views' end");
 
 struct Bufs {
     __amdgpu_buffer_rsrc_t in, out;
 };
+
+// The item span rule of quic_pp.h (Buffers), one wording for k_gcm and
+// k_chacha: a packet's input extent (header + payload, + tag for unprotect)
+// and output extent (header + payload, + tag for protect) at its offsets
+// ioff / ooff from the item's lowest ones must end inside the views.  Every
+// buffer load of a packet ends at or before its input extent's end (partial
+// tail blocks are loaded end-aligned or run into the tag) and every buffer
+// store at or before its output extent's end, so a packet that passes never
+// meets the views' end.
+template <bool ENC>
+__device__ __forceinline__ bool item_span_ok(const Pkt &P, uint64_t ioff, uint64_t ooff)
+{
+    const uint64_t body = (uint64_t)(P.hlen + P.clen);
+    return ioff + body + (ENC ? 0 : QPP_TAG_LEN) <= kBufBytes &&
+           ooff + body + (ENC ? QPP_TAG_LEN : 0) <= kBufBytes;
+}
 
 // --------------------------------------------------------------- AES-GCM --
 
@@ -1716,9 +1733,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
                 for (int i = 0; i < 4 * (kNR + 1); ++i)
                     rk[i] = __builtin_amdgcn_readfirstlane((i >= 12 && i < 4 * kNR) ? ks->rkr[i] : ks->rk[i]);
                 const uint64_t ioff = d.in_off - bi, ooff = d.out_off - bo;
-                const uint64_t rlen = (uint64_t)(P.hlen + P.clen + (ENC ? 0 : QPP_TAG_LEN));
-                const uint64_t wlen = (uint64_t)(P.hlen + P.clen + QPP_TAG_LEN);
-                if (ioff + rlen <= kBufBytes && ooff + wlen <= kBufBytes) {
+                if (item_span_ok<ENC>(P, ioff, ooff)) {
                     const Bufs B{
                         __builtin_amdgcn_make_buffer_rsrc((void *)(gin + bi), 0, (int)kBufBytes, 0x00020000),
                         __builtin_amdgcn_make_buffer_rsrc((void *)(gout + bo), 0, (int)kBufBytes, 0x00020000)};
@@ -1931,10 +1946,8 @@ __device__ __forceinline__ void chacha_wave(const WaveSpan &W, ChachaSmem<WG> &s
             // would be hoisted out of the loop and held live across it
             const uint32_t tf = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) << 6 | lane_fresh();
             const uint64_t ioff = d.in_off - bi, ooff = d.out_off - bo;
-            if (P.status == QPP_S_OK &&
-                (ioff + (uint64_t)(P.hlen + P.clen + QPP_TAG_LEN) > kBufBytes ||
-                 ooff + (uint64_t)(P.hlen + P.clen + QPP_TAG_LEN) > kBufBytes))
-                P.status = QPP_S_LENGTH;  // the wave's packets span more than 4 GiB
+            if (P.status == QPP_S_OK && !item_span_ok<ENC>(P, ioff, ooff))
+                P.status = QPP_S_LENGTH;  // the wave's packets span more than QPP_ITEM_SPAN_MAX
             if (P.status == QPP_S_OK) {
                 *(u32x4 *)(sm.scratch[tf >> 2] + kScrHdr) = pre.h0;
                 const Bufs B{

@@ -7,6 +7,9 @@ AES_128_GCM, AES_256_GCM, CHACHA20_POLY1305 = 0, 1, 2
 PACKET_MAX = 1500
 TAG_LEN = 16
 MAX_HDR = 1500
+# QPP_ITEM_SPAN_MAX: (offset - lowest offset in the item) + extent of every
+# packet of a 16-packet item, for input and output alike (quic_pp.h, Buffers)
+ITEM_SPAN_MAX = 0xFFFFFF00
 
 # the message of a packet the engine gave up on (S_INTERNAL: a kernel's
 # bounded wait ran out; never expected)

@@ -17,10 +17,19 @@
  *
  * Buffers: the device-pointer launches (qpp_protect, qpp_unprotect and the
  * planned forms) cannot see buffer sizes, so every descriptor's input and
- * output extents must lie inside the caller's allocations, and the 16
- * packets of one wavefront (consecutive descriptors, or consecutive in a
- * plan's bucket order) must lie within 4 GiB of each other (else
- * QPP_S_LENGTH).  The session forms check every descriptor against in_len /
+ * output extents must lie inside the caller's allocations; the buffers
+ * themselves may be of any size.  A packet's input extent is hdr_len + len
+ * bytes at in_off for protect and len bytes for unprotect; its output extent
+ * is hdr_len + len + QPP_TAG_LEN bytes at out_off for protect and
+ * len - QPP_TAG_LEN bytes for unprotect.  The kernels that run 16 packets per
+ * wavefront (an "item": 16 consecutive descriptors, or up to 16 consecutive
+ * in a plan's bucket order) address an item through 32-bit views based at its
+ * lowest offsets, so for every packet of an item
+ *     (offset - lowest offset in the item) + extent <= QPP_ITEM_SPAN_MAX,
+ * separately for input and output.  A packet beyond that gets QPP_S_LENGTH
+ * and nothing of it is written; the item's other packets are not affected.
+ * Launches that run one packet per wavefront (small unplanned launches) have
+ * no such limit.  The session forms check every descriptor against in_len /
  * out_len and report QPP_S_LENGTH for one that does not fit, without touching
  * memory for it.
  *
@@ -52,6 +61,7 @@ extern "C" {
 #define QPP_PACKET_MAX 1500      /* _crypto.c:13 PACKET_LENGTH_MAX */
 #define QPP_TAG_LEN 16           /* _crypto.c:11 AEAD_TAG_LENGTH */
 #define QPP_MAX_HDR 1500         /* longest header / associated data the kernels accept */
+#define QPP_ITEM_SPAN_MAX 0xffffff00u /* bytes one 16-packet item may span (see Buffers above) */
 
 /* return codes of the API calls */
 #define QPP_OK 0

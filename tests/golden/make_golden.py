@@ -46,7 +46,7 @@ def load_ref():
     return mod
 
 
-REF = load_ref()
+REF = None  # loaded by main(): importing this module (tests/test_pn_decode.py) needs no reference build
 
 
 def _hash(suite):
@@ -138,6 +138,8 @@ def run_case(c):
 
 
 def main():
+    global REF
+    REF = load_ref()
     cases = build_cases()
     out = []
     for c in cases:

@@ -86,8 +86,10 @@ def protect_all(ref, w) -> np.ndarray:
 
 def unprotect_all(ref, w, wire: np.ndarray):
     """(plaintext image, decoded packet numbers) of every packet of w's wire
-    image; a failed packet raises (the batch is expected to authenticate)."""
-    from aioquic_amd.packet import decode_packet_number
+    image; a failed packet raises (the batch is expected to authenticate).
+    The truncated number is decoded by the oracle (qo_decode_pn, pinned to the
+    reference's function by tests/test_pn_decode.py), never by the product."""
+    from oracle.oracle import decode_pn as decode_packet_number
 
     objs = _objects(ref, w.keys)
     out = bytearray(w.plain_size)

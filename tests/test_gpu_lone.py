@@ -387,3 +387,56 @@ def test_lone_threshold_sizes_whole_batch(L, suite, n):
         m = min(n, 512)
         o_wire, _ = orc.protect_batch(w.keys, w.desc[:m], w.plain, w.wire_size)
         assert np.array_equal(o_wire[: m * 1200], wire[: m * 1200])
+
+
+@pytest.mark.parametrize("suite,n", [(0, 8193), (0, 4096), (1, 4096), (2, 65)],
+                         ids=["aes128-8193-quad", "aes128-4096-lone", "aes256-4096-lone", "chacha-65-quad"])
+def test_whole_batch_expected_pn_is_not_the_pn(L, suite, n):
+    """The threshold workloads again, unprotected with expected packet numbers
+    that are NOT the packet numbers: each moved by a seeded offset of up to
+    +-32767, under half the 2-byte window of the workload's headers (0x41:
+    pn_len 2, window 65536), floored at 0.  Every packet's decoded number and
+    plaintext against the reference's own _crypto with the oracle's decode
+    (tests/ref_crypto.py; the C oracle on a prefix without oracle/_ref)."""
+    import dataclasses
+
+    import torch
+
+    from aioquic_amd import bench_data
+    from aioquic_amd.batch import PacketEngine
+    from tests import ref_crypto
+
+    w = bench_data.make_workload(n, suite=suite, n_keys=3, seed=0x7E + n, order="random")
+    assert (w.plain.reshape(n, bench_data.SLOT_BYTES)[:, 0] & 3 == 1).all()  # pn_len 2
+    rng = np.random.default_rng(0xE0 + n)
+    moved = w.desc["pn"].astype(np.int64) + rng.integers(-32767, 32768, size=n)
+    ud = w.udesc.copy()
+    ud["pn"] = np.maximum(moved, 0).astype(np.uint64)
+    assert (ud["pn"] != w.desc["pn"]).sum() > n * 0.9
+    w2 = dataclasses.replace(w, udesc=ud)
+    eng = PacketEngine(w.n_keys)
+    eng.set_key_records(w.keys)
+    dev = torch.device("cuda")
+    d_wire = torch.zeros(w.wire_size, dtype=torch.uint8, device=dev)
+    d_back = torch.zeros(w.plain_size, dtype=torch.uint8, device=dev)
+    d_res = torch.zeros(n * 16, dtype=torch.uint8, device=dev)
+    d_res2 = torch.zeros(n * 16, dtype=torch.uint8, device=dev)
+    eng.protect(torch.from_numpy(w.desc.view(np.uint8)).to(dev), n, torch.from_numpy(w.plain).to(dev), d_wire, d_res)
+    eng.unprotect(torch.from_numpy(ud.view(np.uint8)).to(dev), n, d_wire, d_back, d_res2)
+    torch.cuda.synchronize()
+    wire, back = d_wire.cpu().numpy(), d_back.cpu().numpy()
+    r2 = d_res2.cpu().numpy().view(L.RESULT)
+    assert (r2["status"] == 0).all()
+    assert np.array_equal(r2["pn"], w.desc["pn"]) and np.array_equal(back, w.plain)
+    ref = ref_crypto.checker(os.environ.get("PYTEST_CURRENT_TEST", "?").split(" ")[0])
+    if ref is not None:
+        assert np.array_equal(ref_crypto.protect_all(ref, w), wire)
+        r_back, r_pn = ref_crypto.unprotect_all(ref, w2, wire)
+        assert np.array_equal(r_back, back) and np.array_equal(r_pn, r2["pn"])
+    else:
+        from oracle import oracle as orc
+
+        m = min(n, 512)
+        o_back, o_res = orc.unprotect_batch(w.keys, ud[:m], wire, w.plain_size)
+        assert (o_res == r2[:m]).all()
+        assert np.array_equal(o_back[: m * 1200], back[: m * 1200])
