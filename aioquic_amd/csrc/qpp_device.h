@@ -576,16 +576,20 @@ __device__ __forceinline__ void aes_ctr2(const CtrCache &c, uint32_t cb0, uint32
 // --------------------------------------------------------------- GHASH ----
 
 // x * H^p using the 32 windowed tables of power p at LDS byte offset `tab`.
-// Entry address = tab + w*256 + v*16: the w*256 part folds into the ds_read
-// immediate; (word & 0xF0F0F0F0) already holds high-nibble*16 per byte.
+// Entry address = tab + w*256 + v*16: a word's 8 window rows fold into the
+// ds_read immediate; (word & 0xF0F0F0F0) already holds high-nibble*16 per byte.
+// `tab` may differ by lane (the GCM close: lane j of a quad multiplies by
+// H^(4-j), one code path for the four tables).  One input word (8 reads, 32
+// VGPRs in flight) at a time, as ghash_mul_global and for its reason.
 __device__ __forceinline__ u32x4 ghash_mul(u32x4 x, const uint8_t *lds, uint32_t tab)
 {
     u32x4 acc = {0, 0, 0, 0};
     uint32_t xw[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
+#pragma unroll 1
     for (int d = 0; d < 4; ++d) {
-        uint32_t hi = xw[d] & 0xF0F0F0F0u;
-        uint32_t lo = (xw[d] << 4) & 0xF0F0F0F0u;
+        const uint32_t w = d == 0 ? xw[0] : d == 1 ? xw[1] : d == 2 ? xw[2] : xw[3];
+        uint32_t hi = w & 0xF0F0F0F0u;
+        uint32_t lo = (w << 4) & 0xF0F0F0F0u;
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
             const int wlo = 2 * (4 * d + b), whi = wlo + 1;

@@ -530,6 +530,8 @@ struct GhashTabs {
     const uint8_t *gtab;    // every slot's tables, global memory
     const uint32_t *wslot;  // LDS: the wave's key slot
     const uint32_t *went;   // LDS: the wave's table entry
+    const uint8_t *ctab;    // close-from-LDS launches: LDS copy of one slot's 4-bit tables
+    const uint32_t *cslot;  // ... and the slot it holds
     __device__ __forceinline__ uint32_t t4() const
     {
         return __builtin_amdgcn_readfirstlane(lds_ld(went)) * (uint32_t)kGhLdsEntry;
@@ -539,6 +541,11 @@ struct GhashTabs {
     {
         const uint32_t s = __builtin_amdgcn_readfirstlane(lds_ld(wslot));
         return gtab + (size_t)s * kGhashTabBytes + pw * (uint32_t)kGhashPowBytes;
+    }
+    // whether ctab holds the wave's slot (wave-uniform)
+    __device__ __forceinline__ bool close_resident() const
+    {
+        return __builtin_amdgcn_readfirstlane(lds_ld(cslot)) == __builtin_amdgcn_readfirstlane(lds_ld(wslot));
     }
 };
 
@@ -625,10 +632,11 @@ __device__ __forceinline__ void write_header_v(const Pkt &P, int sub, bool maske
 // GHASH tables of the packet's key slot: the step loop multiplies by H^4 from
 // one of the workgroup's LDS table entries; the few multiplies outside the
 // loop (associated data beyond 16 bytes by H^1, each lane's closing H^(4-j))
-// read the slot's tables in global memory.
+// read the slot's tables in global memory, or (CLDS, see gcm_tab_entries) the
+// workgroup's LDS copy of them.
 // PRIO (k_gcm with 512-thread workgroups: launches of at most one item per
 // wave): the step loop sets the wave's issue priority by its progress.
-template <int NR, bool ENC, int BPL, int SUITE, bool PRIO>
+template <int NR, bool ENC, int BPL, int SUITE, bool PRIO, bool CLDS = false>
 __device__ __forceinline__ u32x4 gcm_packet(const Pkt &P, const KeySlot *ks, const u32x4 h0,
                                             const uint32_t *rk, int sub, const GhashTabs &G,
                                             const uint8_t *te, const Bufs &B, uint32_t ioff, uint32_t ooff,
@@ -659,6 +667,16 @@ __device__ __forceinline__ u32x4 gcm_packet(const Pkt &P, const KeySlot *ks, con
         nxt1 = __builtin_amdgcn_raw_buffer_load_b128(B.in, (int)ct_load(sub - q + 4), 0, 0);
     }
 
+    // x * H^(pw + 1), pw possibly different in each lane: the multiplies
+    // outside the step loop.  From the workgroup's LDS copy of the 4-bit tables
+    // when it holds this wave's slot (CLDS launches; read where used, not
+    // kept live across the step loop), else from the slot's global tables.
+    auto mul_pow = [&](u32x4 x, uint32_t pw) -> u32x4 {
+        if constexpr (CLDS) {
+            if (G.close_resident()) return ghash_mul(x, G.ctab, pw * (uint32_t)kGhashPowBytes);
+        }
+        return ghash_mul_global(x, G.global(pw));
+    };
     // fold the associated data (unmasked for unprotect) into Z
     u32x4 z = {0, 0, 0, 0};
     for (int g = 0; g < n_a; ++g) {
@@ -675,7 +693,7 @@ __device__ __forceinline__ u32x4 gcm_packet(const Pkt &P, const KeySlot *ks, con
         }
         a = keep_bytes(a, min(16, hlen - 16 * g));
         if (!ENC && P.hp) a ^= hp_pattern(16 * g, P.mask, P.fbm, P.pn_off, P.pn_len);
-        if (g > 0) z = ghash_mul_global(z, G.global(0));  // H^1
+        if (g > 0) z = mul_pow(z, 0u);  // H^1
         z ^= a;
     }
     // the header out: unprotect (mask known) and protect without HP now;
@@ -690,12 +708,12 @@ __device__ __forceinline__ u32x4 gcm_packet(const Pkt &P, const KeySlot *ks, con
     const uint32_t lens_h = bswap((uint32_t)hlen * 8u);
 
     // The last step: lane j closes its Horner chain with H^(4-j) (the slot's
-    // global table of power 3 - j), and the lengths block's lane (lane 3, the
+    // 4-bit table of power 3 - j), and the lengths block's lane (lane 3, the
     // last position of the sequence) adds E_K(J0), which its AES slot just
     // produced (keystream ksl): the tag is then the quad's xor of acc
     auto close = [&](u32x4 ksl) {
         const uint32_t lf = lane_fresh();
-        acc = ghash_mul_global(acc, G.global(3u - (lf & 3)));
+        acc = mul_pow(acc, 3u - (lf & 3));
         if ((lf & 3) == 3) acc ^= ksl;
     };
     // the output side of one block given its keystream: CT block i (input
@@ -1414,9 +1432,21 @@ __device__ __forceinline__ void write_result(qpp_result *res, uint32_t p, int su
 constexpr int kTabEntries = 4;
 // Two 512-thread workgroups per CU (launch_packets: small single-key
 // launches) hold one table entry each.
-template <int WG>
-constexpr int gcm_tab_entries() { return WG == 512 ? 1 : kTabEntries; }
+//
+// Close-from-LDS form (CLDS; launch_packets: unplanned 1024-thread launches
+// with one key of the suite in the table): one H^4 entry, and in the space of
+// the other three a copy of one slot's 4-bit-window tables of H^1..H^4
+// (32 KiB, the bytes ghash_mul_global reads), fetched with the first entry
+// load of the workgroup.  The packets of that slot then take their
+// multiplies outside the step loop (associated data, each lane's closing
+// H^(4-j)) from LDS instead of 32 gathered global loads per lane
+// (gcm_packet); a packet of any other slot keeps the global tables.
+template <int WG, bool CLDS = false>
+constexpr int gcm_tab_entries() { return (WG == 512 || CLDS) ? 1 : kTabEntries; }
 static_assert(kGhLdsEntry % 1024 == 0, "LDS-DMA pieces of 1 KiB");
+constexpr int kCloseTabBytes = kGhashPowers * kGhashPowBytes;
+static_assert(kCloseTabBytes % 1024 == 0 && kCloseTabBytes <= (kTabEntries - 1) * kGhLdsEntry,
+              "the close tables fit the space of the H^4 entries they replace");
 
 // Watchdog events since the library loaded (tab_acquire gave up on a GHASH
 // table entry, or a pair launch's hand-over timed out: the packets concerned
@@ -1435,12 +1465,16 @@ __device__ uint32_t g_qpp_spin_lone = 1u << 18;
 // every product run.
 __device__ uint32_t g_qpp_pair_delay = 0u;
 
-template <int WG, int NE = gcm_tab_entries<WG>()>
+template <int WG, bool CLDS = false, int NE = gcm_tab_entries<WG, CLDS>()>
 struct __attribute__((aligned(16))) GcmSmem {
+    static constexpr int kEntries = NE;
+    static constexpr bool kClose = CLDS;
     // GHASH table entries first (LDS offset 0: the entry's offset rides in
     // the 5-bit window address), then the AES image, whose base stays within
     // the 16-bit ds_read immediate range
     uint8_t h4[NE][kGhLdsEntry];              // 14 KiB each
+    uint8_t ctab[CLDS ? kCloseTabBytes : 0];  // CLDS: slot cslot's 4-bit tables of H^1..H^4   32 KiB
+    uint32_t cslot[CLDS ? 4 : 0];             // CLDS: [0] the slot ctab holds (kNoSlot: none yet)
     uint8_t te[kTeBytes];                     // Te0|Te1 x 32 bank copies   64 KiB
     uint32_t eslot[NE];                       // slot held by entry e (kNoSlot: none)
     uint32_t eref[NE];                        // waves running entry e's slot
@@ -1462,8 +1496,8 @@ struct __attribute__((aligned(16))) GcmSmem {
 // before the table has landed, to overlap its LDS-DMA with the packets'
 // descriptors and headers, measured 2-4 % slower at 64 Ki: those loads queue
 // behind the DMA in the vector memory counter, profiles/r4d_ab_tab_defer.txt.)
-template <int WG>
-__device__ uint32_t tab_acquire(GcmSmem<WG> &sm, const uint8_t *gtab, uint32_t cur)
+template <class SM>
+__device__ uint32_t tab_acquire(SM &sm, const uint8_t *gtab, uint32_t cur)
 {
     const uint32_t spin = __builtin_nontemporal_load(&g_qpp_spin_tab);
     typedef const __attribute__((address_space(1))) void *gptr_t;
@@ -1480,7 +1514,7 @@ __device__ uint32_t tab_acquire(GcmSmem<WG> &sm, const uint8_t *gtab, uint32_t c
             int hit = -1, vic = -1;
             uint32_t best = 0xffffffffu;
 #pragma unroll
-            for (int i = 0; i < gcm_tab_entries<WG>(); ++i) {
+            for (int i = 0; i < SM::kEntries; ++i) {
                 const uint32_t s = lds_ld(&sm.eslot[i]);
                 const uint32_t r = lds_ld(&sm.eref[i]);
                 const uint32_t u = lds_ld(&sm.eused[i]);
@@ -1495,6 +1529,14 @@ __device__ uint32_t tab_acquire(GcmSmem<WG> &sm, const uint8_t *gtab, uint32_t c
                 ld = 1;
                 lds_st(&sm.eslot[vic], cur);
                 lds_st(&sm.eready[vic], 0u);
+                if constexpr (SM::kClose) {
+                    // the workgroup's first entry load brings the slot's
+                    // close tables with it (once: they are never replaced)
+                    if (lds_ld(&sm.cslot[0]) == kNoSlot) {
+                        lds_st(&sm.cslot[0], cur);
+                        ld = 3;
+                    }
+                }
             }
             if (hit >= 0) {
                 got = (uint32_t)hit;
@@ -1523,6 +1565,17 @@ __device__ uint32_t tab_acquire(GcmSmem<WG> &sm, const uint8_t *gtab, uint32_t c
         for (int c = 0; c < kGhLdsEntry / 1024; ++c)
             __builtin_amdgcn_global_load_lds((gptr_t)(src + c * 1024 + l * 16), (lptr_t)(sm.h4[e] + c * 1024),
                                              16, 0, 0);
+        if constexpr (SM::kClose) {
+            // H^1..H^4 in 4-bit windows, as they lie in global memory; landed,
+            // like the entry, before any wave is told the entry is ready
+            if (load & 2u) {
+                const uint8_t *src4 = gtab + (size_t)cur * kGhashTabBytes;
+#pragma unroll 4
+                for (int c = 0; c < kCloseTabBytes / 1024; ++c)
+                    __builtin_amdgcn_global_load_lds((gptr_t)(src4 + c * 1024 + l * 16),
+                                                     (lptr_t)(sm.ctab + c * 1024), 16, 0, 0);
+            }
+        }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (lane_fresh() == 0) lds_st(&sm.eready[e], 1u);
     } else {
@@ -1545,8 +1598,8 @@ __device__ uint32_t tab_acquire(GcmSmem<WG> &sm, const uint8_t *gtab, uint32_t c
     return e;
 }
 
-template <int WG>
-__device__ __forceinline__ void tab_release(GcmSmem<WG> &sm, uint32_t e)
+template <class SM>
+__device__ __forceinline__ void tab_release(SM &sm, uint32_t e)
 {
     if (lane_fresh() == 0) atomicSub(&sm.eref[e], 1u);
 }
@@ -1594,7 +1647,7 @@ constexpr uint32_t kPoolDiv = QPP_POOL_DIV;
 #define QPP_PRIO512 1  // study switch: issue priority by progress in the 512-thread shape
 #endif
 
-template <int SUITE, bool ENC, int WG, int BPL>
+template <int SUITE, bool ENC, int WG, int BPL, bool CLDS = false>
 __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_gcm(const KeySlot *__restrict__ slots,
                                               const uint8_t *__restrict__ gtab, uint32_t cap,
                                               const qpp_desc *__restrict__ desc, uint32_t n,
@@ -1621,14 +1674,15 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
     const uint32_t per = (stat + gridDim.x - 1) / gridDim.x;
     const uint32_t sb = ib + min(stat, per * blockIdx.x), se = ib + min(stat, per * (blockIdx.x + 1));
     if (!pool && sb >= se) return;  // uniform over the workgroup
-    __shared__ GcmSmem<WG> sm;
+    static_assert(!CLDS || WG == 1024, "the 512-thread shape has no LDS to spare for the close tables");
+    __shared__ GcmSmem<WG, CLDS> sm;
     // Thread-derived values are recomputed where they are used, from the
     // wave index (an SGPR) and a fresh lane id, instead of being kept live
     // across the packet loops: at 128 VGPRs anything live across the GCM step
     // loop is spilled to scratch (HBM traffic and latency).
     auto tid_now = [&]() -> uint32_t { return (wv << 6) | lane_fresh(); };
     load_te<WG>(sm.te);
-    if (threadIdx.x < gcm_tab_entries<WG>()) {
+    if (threadIdx.x < gcm_tab_entries<WG, CLDS>()) {
         sm.eslot[threadIdx.x] = kNoSlot;
         sm.eref[threadIdx.x] = 0u;
         sm.eready[threadIdx.x] = 0u;
@@ -1639,6 +1693,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
         sm.tick = 0u;
         sm.next = sb;
         sm.exited = 0u;
+        if constexpr (CLDS) sm.cslot[0] = kNoSlot;
     }
     if (threadIdx.x < WG / 64) sm.wslot[threadIdx.x] = kNoSlot;
     __syncthreads();
@@ -1737,13 +1792,13 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
                     const Bufs B{
                         __builtin_amdgcn_make_buffer_rsrc((void *)(gin + bi), 0, (int)kBufBytes, 0x00020000),
                         __builtin_amdgcn_make_buffer_rsrc((void *)(gout + bo), 0, (int)kBufBytes, 0x00020000)};
-                    const GhashTabs G{&sm.h4[0][0], gtab, &sm.wslot[wv], &sm.went[wv]};
+                    const GhashTabs G{&sm.h4[0][0], gtab, &sm.wslot[wv], &sm.went[wv], sm.ctab, sm.cslot};
                     QPP_PROBE_AT(3);
                     // unprotect: what the results need after the loop
                     const uint64_t pn = P.pn;
                     const int hlen = P.hlen;
                     u32x4 got_tag;
-                    const u32x4 tag = gcm_packet<kNR, ENC, BPL, SUITE, WG == 512 && QPP_PRIO512>(P, ks, pre.h0, rk, t1 & 3, G, sm.te, B,
+                    const u32x4 tag = gcm_packet<kNR, ENC, BPL, SUITE, WG == 512 && QPP_PRIO512, CLDS>(P, ks, pre.h0, rk, t1 & 3, G, sm.te, B,
                                                                        (uint32_t)ioff, (uint32_t)ooff, got_tag
 #if QPP_COMBO_PRIO
                                                                        , pbase
@@ -1807,10 +1862,10 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
                 QPP_PROBE_AT(1);
                 // release before acquiring: a wave never waits holding an entry
                 if (held != kNoSlot) {
-                    tab_release<WG>(sm, __builtin_amdgcn_readfirstlane(lds_ld(&sm.went[wv])));
+                    tab_release(sm, __builtin_amdgcn_readfirstlane(lds_ld(&sm.went[wv])));
                     if (lane_fresh() == 0) lds_st(&sm.wslot[wv], kNoSlot);
                 }
-                const uint32_t e = tab_acquire<WG>(sm, gtab, cur);
+                const uint32_t e = tab_acquire(sm, gtab, cur);
                 if (e == kNoSlot) {
                     // the watchdog gave up: the slot's packets are not
                     // processed and report QPP_S_INTERNAL (no stale result
@@ -1837,7 +1892,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
         }
     }
     if (__builtin_amdgcn_readfirstlane(lds_ld(&sm.wslot[wv])) != kNoSlot)
-        tab_release<WG>(sm, __builtin_amdgcn_readfirstlane(lds_ld(&sm.went[wv])));
+        tab_release(sm, __builtin_amdgcn_readfirstlane(lds_ld(&sm.went[wv])));
     // the last wave of the last workgroup zeroes the pool for its next launch
     // (every wave has taken its last ticket by then)
     if (pool && lane_fresh() == 0 && atomicAdd(&sm.exited, 1u) == (uint32_t)(WG / 64 - 1) &&
@@ -2806,6 +2861,9 @@ static bool pool_choice()
 // Launches that found every pool slot held and ran on static shares alone
 // (qpp_pool_fallbacks; tests/test_gpu_pool.py).
 static std::atomic<uint64_t> g_pool_fallbacks{0};
+// GCM launches that took the close-from-LDS form of k_gcm
+// (qpp_close_lds_launches; tests/test_gpu_close_lds.py).
+static std::atomic<uint64_t> g_close_lds_launches{0};
 
 // A free pool slot (its counters zero) or -1.
 static int pool_acquire(const qpp_keytab *kt)
@@ -2916,6 +2974,7 @@ extern "C" {
 int qpp_abi_version(void) { return QPP_ABI_VERSION; }
 
 uint64_t qpp_pool_fallbacks(void) { return g_pool_fallbacks.load(std::memory_order_relaxed); }
+uint64_t qpp_close_lds_launches(void) { return g_close_lds_launches.load(std::memory_order_relaxed); }
 
 uint32_t qpp_watchdog_count(void)
 {
@@ -3279,25 +3338,29 @@ static int launch_packets(bool enc, const qpp_keytab *kt, const qpp_desc *d_desc
     const bool lone = !plan && lone_choice();
     const dim3 lgrid((n + kLoneWG / 64 - 1) / (kLoneWG / 64)), lblock(kLoneWG);
     const LoneStage lst = stage ? *stage : LoneStage{nullptr, nullptr, 0u};
-#define QPP_LAUNCH_GCM_W(SUITE, BPLV, WGV)                                                     \
+#define QPP_LAUNCH_GCM_W(SUITE, BPLV, WGV, CLDSV)                                              \
     do {                                                                                       \
         const dim3 grid(gcm_grid(waves, WGV / 64)), block(WGV);                                 \
         const int psl = (WGV == 1024 || QPP_POOL512) && kt->n_suite[SUITE] == 1 ? pool_acquire(kt) : -1; \
         uint32_t *pl = psl >= 0 ? kt->pool->d + (size_t)psl * kPoolStride : nullptr;          \
+        if (CLDSV) g_close_lds_launches.fetch_add(1, std::memory_order_relaxed);               \
         if (enc)                                                                               \
-            hipLaunchKernelGGL((k_gcm<SUITE, true, WGV, BPLV>), grid, block, 0, s,             \
+            hipLaunchKernelGGL((k_gcm<SUITE, true, WGV, BPLV, CLDSV>), grid, block, 0, s,      \
                                kt->d_slots, kt->d_gtab, kt->cap, d_desc, n, d_in, d_out, d_res, \
                                d_items, d_irange, pl);                                         \
         else                                                                                   \
-            hipLaunchKernelGGL((k_gcm<SUITE, false, WGV, BPLV>), grid, block, 0, s,            \
+            hipLaunchKernelGGL((k_gcm<SUITE, false, WGV, BPLV, CLDSV>), grid, block, 0, s,     \
                                kt->d_slots, kt->d_gtab, kt->cap, d_desc, n, d_in, d_out, d_res, \
                                d_items, d_irange, pl);                                         \
         pool_release(kt, psl, s);                                                              \
     } while (0)
+    // 1024 threads: unplanned with one key of the suite in the table, the
+    // close-from-LDS form (three of its four H^4 entries would sit idle)
 #define QPP_LAUNCH_GCM_B(SUITE, BPLV)                                                          \
     do {                                                                                       \
-        if (BPLV == 2 && gcm_two_wg(kt, SUITE, waves)) QPP_LAUNCH_GCM_W(SUITE, BPLV, 512);       \
-        else QPP_LAUNCH_GCM_W(SUITE, BPLV, kGcmWG);                                             \
+        if (BPLV == 2 && gcm_two_wg(kt, SUITE, waves)) QPP_LAUNCH_GCM_W(SUITE, BPLV, 512, false); \
+        else if (!plan && kt->n_suite[SUITE] == 1) QPP_LAUNCH_GCM_W(SUITE, BPLV, kGcmWG, true);  \
+        else QPP_LAUNCH_GCM_W(SUITE, BPLV, kGcmWG, false);                                      \
     } while (0)
 #define QPP_LAUNCH_GCM(SUITE)                                                                  \
     if (mask & (1u << SUITE)) {                                                                \

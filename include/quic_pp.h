@@ -161,6 +161,11 @@ uint32_t qpp_watchdog_count(void);
  * flight and so ran without the launch-wide item pool (static shares only;
  * the same bytes, a possibly longer tail).  Diagnostic. */
 uint64_t qpp_pool_fallbacks(void);
+/* AES-GCM launches (process-wide, since the library loaded) that ran the
+ * kernel form whose closing GHASH multiplies read an LDS copy of the key's
+ * tables: unplanned 1024-thread launches with one key of the suite in the
+ * table.  The same bytes as the other form.  Diagnostic. */
+uint64_t qpp_close_lds_launches(void);
 const char *qpp_strerror(int rc);
 int qpp_device_check(void);             /* QPP_OK if the current device is gfx950 */
 
