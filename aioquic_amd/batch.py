@@ -74,6 +74,18 @@ class PacketEngine:
         km = self.table.derive(np.ascontiguousarray(secrets).tobytes())
         return np.frombuffer(km, dtype=L.KEY_MATERIAL).copy()
 
+    def derive_initial_keys(self, records: np.ndarray):
+        """Batched CryptoPair.setup_initial on the device
+        (qpp_keytab_derive_initial): `records` are layout.INITIAL records.
+        Returns (km, secrets): km[i, 0] / km[i, 1] the KEY_MATERIAL of record
+        i's "client in" / "server in" keys (shape (n, 2)), secrets (n, 2, 32)
+        uint8.  Directions given SLOT_NONE are returned but not installed."""
+        assert records.dtype == L.INITIAL
+        km, sec = self.table.derive_initial(np.ascontiguousarray(records).tobytes())
+        n = len(records)
+        return (np.frombuffer(km, dtype=L.KEY_MATERIAL).reshape(n, 2).copy(),
+                np.frombuffer(sec, dtype=np.uint8).reshape(n, 2, 32).copy())
+
     def set_key_records(self, recs: np.ndarray) -> None:
         assert recs.dtype == L.KEY_MATERIAL
         self.table.set(np.ascontiguousarray(recs).tobytes())

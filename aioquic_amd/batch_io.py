@@ -50,7 +50,8 @@ from ._crypto import CryptoError, KeyTable, protect_list, unprotect_list, unprot
 from .crypto import CryptoContext, CryptoPair, KeyUnavailableError, next_key_phase
 from .packet import decode_packet_number
 
-__all__ = ["SendBatch", "ReceiveBatch", "KeySlots", "ReservedBitsError", "ConnectionClosedError"]
+__all__ = ["SendBatch", "ReceiveBatch", "KeySlots", "setup_initial_batch", "ReservedBitsError",
+           "ConnectionClosedError"]
 
 # host-side statuses of the C receive walks (_crypto_ext.c WALK_S_*)
 _S_RESERVED, _S_CLOSED = 0x101, 0x102
@@ -151,6 +152,33 @@ class KeySlots:
         self.commit()
         return slots
 
+    def reserve(self, n: int) -> list:
+        """n unused slots for keys the caller installs on the table itself
+        (setup_initial_batch), by assign()'s rule: a table that cannot hold n
+        more is cleared and refilled; OverflowError if an empty one cannot
+        either.  The slots stay unused until adopt() binds them."""
+        if self._inbox:
+            self._drain()
+        if n > self.capacity:
+            raise OverflowError("key table full")
+        if n > self.capacity - len(self._keep):
+            self.reset()
+        high = len(self._keep) + len(self._free)
+        take = self._free[::-1][:n]
+        return take + list(range(high, high + n - len(take)))
+
+    def adopt(self, slots, triples) -> None:
+        """Bind reserved slots that already hold their keys on the device to
+        their (aead, hp, key_phase): nothing is left to commit for them."""
+        taken = set(slots)
+        self._free = [s for s in self._free if s not in taken]
+        for s, (aead, hp, key_phase) in zip(slots, triples):
+            ident = (id(aead), id(hp), int(key_phase))
+            self._slot[ident] = s
+            self._keep[s] = (aead, hp)
+            self._by_obj.setdefault(ident[0], []).append(ident)
+            self._by_obj.setdefault(ident[1], []).append(ident)
+
     def release(self, objs) -> None:
         """Forget every slot built from one of `objs` (AEAD or HP objects)
         and clear those device entries."""
@@ -232,6 +260,67 @@ def default_slots() -> KeySlots:
     if t is None:
         t = _per_thread.slots = KeySlots(4096)
     return t
+
+
+def _per_pair(value, n: int, what: str) -> list:
+    """One value for every pair, or one per pair."""
+    if isinstance(value, (list, tuple, np.ndarray)):
+        if len(value) != n:
+            raise ValueError(f"{what}: one value or one per pair")
+        return list(value)
+    return [value] * n
+
+
+def setup_initial_batch(pairs, cids, is_client, versions, slots: Optional[KeySlots] = None) -> None:
+    """The batched CryptoPair.setup_initial (quic/crypto.py:201-227) for the
+    new connections of a batch: ONE device call (KeyTable.derive_initial)
+    derives both directions of every pair from its connection ID and installs
+    them in two slots each of `slots` (default: this thread's default_slots()),
+    where the batched send / receive callers then find them: no KeyTable.set
+    follows.  `is_client` and `versions` are one value or one per pair.  Every
+    context ends as pair.setup_initial(cid, is_client, version) leaves it, and
+    the setup callbacks run with "tls", recv before send, pairs in order.
+    A caller that prepares every supported version (connection.py:1509-1515)
+    lists the connection once per version, each with its own pair."""
+    slots = slots if slots is not None else default_slots()
+    n = len(pairs)
+    if len(cids) != n:
+        raise ValueError("cids: one per pair")
+    roles = [bool(r) for r in _per_pair(is_client, n, "is_client")]
+    vers = _per_pair(versions, n, "versions")
+    if not n:
+        return
+    recs = np.zeros(n, dtype=L.INITIAL)
+    for i, cid in enumerate(cids):
+        if len(cid) > L.CID_MAX:
+            raise ValueError("connection ID longer than 20 bytes")
+        recs["cid"][i, : len(cid)] = np.frombuffer(cid, dtype=np.uint8)
+        recs["cid_len"][i] = len(cid)
+        if vers[i] == crypto_mod.QuicProtocolVersion.VERSION_2:
+            recs["flags"][i] = L.DERIVE_V2
+    taken = slots.reserve(2 * n)
+    recs["slot_client"] = taken[0::2]
+    recs["slot_server"] = taken[1::2]
+    km, secrets = slots.table.derive_initial(recs.tobytes())
+    km = np.frombuffer(km, dtype=L.KEY_MATERIAL)
+    suite = crypto_mod._SUITES[crypto_mod.INITIAL_CIPHER_SUITE]
+    built = []  # per pair: (recv, send), each (slot, secret, aead, hp)
+    for i in range(n):
+        both = []
+        for label in crypto_mod._INITIAL_LABELS[roles[i]]:
+            k = 2 * i + (label == b"server in")
+            m = km[k]
+            aead = crypto_mod.AEAD(suite.aead_name, m["key"][: suite.key_len].tobytes(), m["iv"].tobytes())
+            hp = crypto_mod.HeaderProtection(suite.hp_name, m["hp"][: suite.key_len].tobytes())
+            both.append((int(m["slot"]), secrets[32 * k: 32 * k + 32], aead, hp))
+        built.append(both)
+    # the device slots were written with key phase 0, which is a fresh context's
+    slots.adopt([d[0] for both in built for d in both], [(d[2], d[3], 0) for both in built for d in both])
+    for pair, both, version in zip(pairs, built, vers):
+        for ctx, (_, secret, aead, hp) in zip((pair.recv, pair.send), both):
+            ctx.cipher_suite, ctx.secret, ctx.version = crypto_mod.INITIAL_CIPHER_SUITE, secret, version
+            ctx.aead, ctx.hp = aead, hp
+            ctx._setup_cb("tls")
 
 
 def _raise_status(status: int) -> Exception:

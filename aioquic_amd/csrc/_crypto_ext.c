@@ -16,7 +16,8 @@
  *
  * Batch API (pointers are ints: device pointers for the device forms, host
  * pointers for the *_into forms; the caller keeps the memory alive):
- *   KeyTable(capacity) .set(materials) .derive(secrets) .clear(slots) .capacity
+ *   KeyTable(capacity) .set(materials) .derive(secrets) .derive_initial(records)
+ *                      .derive_trace(enable) .clear(slots) .capacity
  *   Plan(capacity)                                  device scratch of the bucketing step
  *   protect(table, desc_ptr, n, in_ptr, out_ptr, res_ptr, stream[, plan])   -> None
  *   unprotect(...)                                                          -> None
@@ -534,6 +535,58 @@ static PyObject *KT_derive(KeyTableObject *self, PyObject *args)
     return km;
 }
 
+/* KeyTable.derive_initial(records[, stream]) -> (key material, secrets):
+ * batched CryptoPair.setup_initial (qpp_keytab_derive_initial); records = whole
+ * qpp_initial records; two qpp_key_material and two 32-byte secrets per record. */
+static PyObject *KT_derive_initial(KeyTableObject *self, PyObject *args)
+{
+    const char *b;
+    Py_ssize_t len;
+    unsigned long long stream = 0;
+    if (!PyArg_ParseTuple(args, "y#|K", &b, &len, &stream)) return NULL;
+    if (len % (Py_ssize_t)sizeof(qpp_initial) || len / (Py_ssize_t)sizeof(qpp_initial) > (1 << 24)) {
+        PyErr_SetString(PyExc_ValueError, "records must be a whole number (up to 2^24) of 32-byte records");
+        return NULL;
+    }
+    uint32_t n = (uint32_t)(len / (Py_ssize_t)sizeof(qpp_initial));
+    PyObject *km = PyBytes_FromStringAndSize(NULL, 2 * (Py_ssize_t)n * (Py_ssize_t)sizeof(qpp_key_material));
+    PyObject *sec = PyBytes_FromStringAndSize(NULL, 2 * (Py_ssize_t)n * 32);
+    if (!km || !sec) {
+        Py_XDECREF(km);
+        Py_XDECREF(sec);
+        return NULL;
+    }
+    qpp_key_material *out = (qpp_key_material *)PyBytes_AsString(km);
+    uint8_t *sout = (uint8_t *)PyBytes_AsString(sec);
+    int rc;
+    Py_BEGIN_ALLOW_THREADS
+    rc = qpp_keytab_derive_initial(self->kt, (const qpp_initial *)b, n, out, sout, as_ptr(stream));
+    Py_END_ALLOW_THREADS
+    if (rc == QPP_E_ARG)
+        PyErr_SetString(PyExc_ValueError,
+                        "bad initial record (slot out of range or used twice, cid longer than 20, unknown flag)");
+    if (rc == QPP_E_ARG || check_rc(rc) < 0) {
+        Py_DECREF(km);
+        Py_DECREF(sec);
+        return NULL;
+    }
+    PyObject *ret = PyTuple_Pack(2, km, sec);
+    Py_DECREF(km);
+    Py_DECREF(sec);
+    return ret;
+}
+
+/* KeyTable.derive_trace(enable=-1) -> (derive_ms, setup_ms) of the last timed
+ * derive_initial call (qpp_keytab_derive_trace). */
+static PyObject *KT_derive_trace(KeyTableObject *self, PyObject *args)
+{
+    int enable = -1;
+    if (!PyArg_ParseTuple(args, "|i", &enable)) return NULL;
+    float d = 0, k = 0;
+    if (check_rc(qpp_keytab_derive_trace(self->kt, enable, &d, &k)) < 0) return NULL;
+    return Py_BuildValue("dd", (double)d, (double)k);
+}
+
 static PyObject *KT_clear(KeyTableObject *self, PyObject *args)
 {
     const char *b;
@@ -556,6 +609,10 @@ static PyMethodDef KT_methods[] = {
     {"set", (PyCFunction)KT_set, METH_VARARGS, "set(materials, stream=0)"},
     {"clear", (PyCFunction)KT_clear, METH_VARARGS, "clear(slots_u32)"},
     {"derive", (PyCFunction)KT_derive, METH_VARARGS, "derive(secrets, stream=0) -> key material"},
+    {"derive_initial", (PyCFunction)KT_derive_initial, METH_VARARGS,
+     "derive_initial(records, stream=0) -> (key material, secrets)"},
+    {"derive_trace", (PyCFunction)KT_derive_trace, METH_VARARGS,
+     "derive_trace(enable=-1) -> (derive_ms, setup_ms) of the last timed derive_initial"},
     {NULL},
 };
 

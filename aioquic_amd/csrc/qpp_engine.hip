@@ -2761,6 +2761,47 @@ __global__ __launch_bounds__(kDeriveWG) void k_derive(const qpp_secret *__restri
     km[i] = r;
 }
 
+// Batched CryptoPair.setup_initial (quic/crypto.py:201-227), two lanes per
+// connection: lane 2i derives record i's "client in" keys and lane 2i + 1 its
+// "server in" keys (the chains are independent after the extract, which both
+// lanes compute: the same instructions, no divergence).  The salts' HMAC pad
+// states come precomputed from the host in the kernel arguments.  All of it
+// is word-based with constant indices (qpp_hkdf::derive_initial): registers
+// only.  km[2i], km[2i + 1]: the key material, secrets[2i], [2i + 1]: the
+// 32-byte secrets, both written as whole words.
+constexpr int kInitialWG = 64;
+
+__global__ __launch_bounds__(kInitialWG) void k_derive_initial(const qpp_initial *__restrict__ ini,
+                                                               uint32_t n,
+                                                               const qpp_hkdf::InitialSalts salts,
+                                                               qpp_key_material *__restrict__ km,
+                                                               uint32_t *__restrict__ secrets)
+{
+    const uint32_t t = blockIdx.x * kInitialWG + threadIdx.x;
+    const uint32_t i = t >> 1;
+    if (i >= n) return;
+    const bool server = t & 1;
+    const qpp_initial &r = ini[i];
+    qpp_hkdf::InitialKeys k;
+    qpp_hkdf::derive_initial(salts, r.cid, r.cid_len, (r.flags & QPP_DERIVE_V2) != 0, server, k);
+    // qpp_key_material as 21 words: slot | suite, key_phase, rsv | iv | key | hp
+    static_assert(sizeof(qpp_key_material) == 84 && offsetof(qpp_key_material, iv) == 8 &&
+                      offsetof(qpp_key_material, key) == 20 && offsetof(qpp_key_material, hp) == 52,
+                  "k_derive_initial writes qpp_key_material by words");
+    uint32_t *o = (uint32_t *)(km + t);
+    o[0] = server ? r.slot_server : r.slot_client;
+    o[1] = QPP_AES_128_GCM;  // suite 0, key_phase 0
+#pragma unroll
+    for (int j = 0; j < 3; ++j) o[2 + j] = __builtin_bswap32(k.iv[j]);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[5 + j] = j < 4 ? __builtin_bswap32(k.key[j]) : 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[13 + j] = j < 4 ? __builtin_bswap32(k.hp[j]) : 0;
+    uint32_t *s = secrets + (size_t)t * 8;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) s[j] = __builtin_bswap32(k.secret[j]);
+}
+
 __global__ void k_clear_slots(KeySlot *slots, const uint32_t *idx, uint32_t n, uint32_t cap)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2846,6 +2887,11 @@ struct qpp_keytab {
     uint8_t *h_suite;      // host mirror: suite of every slot (0xff = empty)
     uint32_t n_suite[3];   // installed slots per suite
     PoolRing *pool;        // item pools of the GCM launches
+    // qpp_keytab_derive_trace: timing events around derive_initial's two
+    // kernels (created on first enable) and the last timed call's durations
+    bool trace;
+    hipEvent_t tev[3];
+    float trace_ms[2];
 };
 
 // QPP_GCM_POOL=0 (a study switch, read once per process): static shares only.
@@ -3048,6 +3094,8 @@ void qpp_keytab_destroy(qpp_keytab *kt)
     if (kt->d_slots) (void)hipFree(kt->d_slots);
     if (kt->d_gtab) (void)hipFree(kt->d_gtab);
     if (kt->d_km) (void)hipFree(kt->d_km);
+    for (hipEvent_t &e : kt->tev)
+        if (e) (void)hipEventDestroy(e);
     if (kt->pool) {
         // (the caller has completed every launch on the table before
         // destroying it, quic_pp.h; the events go with the counters)
@@ -3126,6 +3174,96 @@ int qpp_keytab_derive(qpp_keytab *kt, const qpp_secret *sec, uint32_t n,
     (void)hipFree(d_sec);
     (void)hipGetLastError();
     return rc;
+}
+
+int qpp_keytab_derive_initial(qpp_keytab *kt, const qpp_initial *ini, uint32_t n,
+                              qpp_key_material *km_out, uint8_t *secrets_out, void *stream)
+{
+    if (!kt || (!ini && n)) return QPP_E_ARG;
+    if (n == 0) return QPP_OK;
+    if (n > (1u << 24)) return QPP_E_ARG;  // 2n lanes and records stay far inside 32 bits
+    for (uint32_t i = 0; i < n; ++i) {
+        const qpp_initial &r = ini[i];
+        const bool c_none = r.slot_client == QPP_SLOT_NONE, s_none = r.slot_server == QPP_SLOT_NONE;
+        if ((!c_none && r.slot_client >= kt->cap) || (!s_none && r.slot_server >= kt->cap) ||
+            r.cid_len > QPP_CID_MAX || (r.flags & ~QPP_DERIVE_V2) ||
+            (r.slot_client == r.slot_server && !c_none))
+            return QPP_E_ARG;
+    }
+    // the salts' pad states: the same for every call
+    static const qpp_hkdf::InitialSalts salts = [] {
+        qpp_hkdf::InitialSalts s;
+        qpp_hkdf::initial_salt_pads(s);
+        return s;
+    }();
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n2 = (size_t)2 * n;
+    if (n2 > kt->km_cap) {
+        if (kt->d_km) HIPCHK(hipFree(kt->d_km));
+        kt->d_km = NULL;
+        kt->km_cap = 0;
+        HIPCHK(hipMalloc(&kt->d_km, n2 * sizeof(qpp_key_material)));
+        kt->km_cap = (uint32_t)n2;
+    }
+    // one temporary: the records, then the 2n secrets
+    const size_t ini_bytes = (size_t)n * sizeof(qpp_initial), sec_bytes = n2 * 32;
+    uint8_t *d_tmp = NULL;
+    HIPCHK(hipMalloc(&d_tmp, ini_bytes + sec_bytes));
+    int rc = QPP_OK;
+    if (hipMemcpyAsync(d_tmp, ini, ini_bytes, hipMemcpyHostToDevice, s) != hipSuccess) {
+        rc = QPP_E_HIP;
+    } else {
+        for (uint32_t i = 0; i < n; ++i) {
+            if (ini[i].slot_client != QPP_SLOT_NONE) keytab_note(kt, ini[i].slot_client, QPP_AES_128_GCM);
+            if (ini[i].slot_server != QPP_SLOT_NONE) keytab_note(kt, ini[i].slot_server, QPP_AES_128_GCM);
+        }
+        const bool timed = kt->trace;
+        if (timed) (void)hipEventRecord(kt->tev[0], s);
+        hipLaunchKernelGGL(k_derive_initial, dim3((uint32_t)((n2 + kInitialWG - 1) / kInitialWG)),
+                           dim3(kInitialWG), 0, s, (const qpp_initial *)d_tmp, n, salts, kt->d_km,
+                           (uint32_t *)(d_tmp + ini_bytes));
+        if (timed) (void)hipEventRecord(kt->tev[1], s);
+        // not-installed directions carry QPP_SLOT_NONE >= cap: their workgroups return at once
+        hipLaunchKernelGGL(k_key_setup, dim3((uint32_t)n2), dim3(kSetupWG), 0, s, kt->d_slots,
+                           kt->d_gtab, kt->cap, kt->d_km, (uint32_t)n2);
+        if (timed) (void)hipEventRecord(kt->tev[2], s);
+        if (hipGetLastError() != hipSuccess) rc = QPP_E_HIP;
+        else if (km_out && hipMemcpyAsync(km_out, kt->d_km, n2 * sizeof(qpp_key_material),
+                                          hipMemcpyDeviceToHost, s) != hipSuccess)
+            rc = QPP_E_HIP;
+        else if (secrets_out && hipMemcpyAsync(secrets_out, d_tmp + ini_bytes, sec_bytes,
+                                               hipMemcpyDeviceToHost, s) != hipSuccess)
+            rc = QPP_E_HIP;
+    }
+    // the records and the outputs are caller host memory: finish before returning
+    if (hipStreamSynchronize(s) != hipSuccess && rc == QPP_OK) rc = QPP_E_HIP;
+    if (kt->trace && rc == QPP_OK &&
+        (hipEventElapsedTime(&kt->trace_ms[0], kt->tev[0], kt->tev[1]) != hipSuccess ||
+         hipEventElapsedTime(&kt->trace_ms[1], kt->tev[1], kt->tev[2]) != hipSuccess))
+        kt->trace_ms[0] = kt->trace_ms[1] = 0;
+    (void)hipFree(d_tmp);
+    (void)hipGetLastError();
+    return rc;
+}
+
+int qpp_keytab_derive_trace(qpp_keytab *kt, int enable, float *derive_ms, float *setup_ms)
+{
+    if (!kt) return QPP_E_ARG;
+    if (enable > 0 && !kt->tev[0]) {
+        for (hipEvent_t &e : kt->tev)
+            if (hipEventCreate(&e) != hipSuccess) {
+                (void)hipGetLastError();
+                for (hipEvent_t &f : kt->tev) {
+                    if (f) (void)hipEventDestroy(f);
+                    f = nullptr;
+                }
+                return QPP_E_HIP;
+            }
+    }
+    if (enable >= 0) kt->trace = enable > 0;
+    if (derive_ms) *derive_ms = kt->trace_ms[0];
+    if (setup_ms) *setup_ms = kt->trace_ms[1];
+    return QPP_OK;
 }
 
 int qpp_keytab_clear(qpp_keytab *kt, const uint32_t *slots, uint32_t n, void *stream)

@@ -57,8 +57,21 @@ SECRET = np.dtype(
     ]
 )
 DERIVE_V2 = 1
+# qpp_initial: one connection's Initial keys for KeyTable.derive_initial
+INITIAL = np.dtype(
+    [
+        ("slot_client", "<u4"),
+        ("slot_server", "<u4"),
+        ("cid_len", "u1"),
+        ("flags", "u1"),
+        ("rsv", "u1", (2,)),
+        ("cid", "u1", (20,)),
+    ]
+)
+SLOT_NONE = 0xFFFFFFFF  # QPP_SLOT_NONE: derive this direction but do not install it
+CID_MAX = 20
 assert DESC.itemsize == 40 and RESULT.itemsize == 16 and KEY_MATERIAL.itemsize == 84
-assert SECRET.itemsize == 80
+assert SECRET.itemsize == 80 and INITIAL.itemsize == 32
 
 
 def key_material(slot: int, suite: int, key: bytes, iv: bytes, hp: bytes, key_phase: int = 0):
@@ -85,4 +98,18 @@ def secret_record(slot: int, suite: int, secret: bytes, *, key_phase: int = 0, v
     rec["secret_len"] = len(secret)
     rec["updates"] = updates
     rec["secret"][0, : len(secret)] = np.frombuffer(secret, dtype=np.uint8)
+    return rec
+
+
+def initial_record(slot_client: int, slot_server: int, cid: bytes, *, v2: bool = False):
+    """One qpp_initial: the connection ID a connection's Initial keys come
+    from, and the slots (or SLOT_NONE) of its "client in" / "server in" keys."""
+    if len(cid) > CID_MAX:
+        raise ValueError("connection ID longer than 20 bytes")
+    rec = np.zeros(1, dtype=INITIAL)
+    rec["slot_client"] = slot_client
+    rec["slot_server"] = slot_server
+    rec["cid_len"] = len(cid)
+    rec["flags"] = DERIVE_V2 if v2 else 0
+    rec["cid"][0, : len(cid)] = np.frombuffer(cid, dtype=np.uint8)
     return rec

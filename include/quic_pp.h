@@ -142,6 +142,22 @@ typedef struct qpp_secret {
     uint8_t secret[64];
 } qpp_secret;            /* 80 bytes */
 
+/* One connection's Initial keys for the batched CryptoPair.setup_initial
+ * (qpp_keytab_derive_initial): the destination connection ID the keys come
+ * from and the slots of the two directions. */
+#define QPP_SLOT_NONE 0xffffffffu   /* derive_initial: do not install this direction */
+#define QPP_CID_MAX 20              /* RFC 9000 sec. 17.2 */
+
+typedef struct qpp_initial {
+    uint32_t slot_client;  /* slot for the "client in" keys (a client sends with them, a
+                              server receives with them), or QPP_SLOT_NONE */
+    uint32_t slot_server;  /* slot for the "server in" keys, or QPP_SLOT_NONE */
+    uint8_t cid_len;       /* 0..QPP_CID_MAX */
+    uint8_t flags;         /* QPP_DERIVE_V2: the v2 salt and the "quicv2 key/iv/hp" labels */
+    uint8_t rsv[2];
+    uint8_t cid[20];
+} qpp_initial;             /* 32 bytes */
+
 typedef struct qpp_keytab qpp_keytab;   /* device-resident expanded keys */
 typedef struct qpp_session qpp_session; /* pinned staging + device buffers + stream */
 
@@ -186,6 +202,38 @@ int qpp_keytab_clear(qpp_keytab *kt, const uint32_t *slots, uint32_t n, void *st
  * the derived key material, e.g. for the host-side AEAD objects. */
 int qpp_keytab_derive(qpp_keytab *kt, const qpp_secret *sec, uint32_t n,
                       qpp_key_material *km_out, void *stream);
+/* Batched CryptoPair.setup_initial (quic/crypto.py:201-227) for n connections
+ * at once, e.g. every new connection of a receive batch, once per supported
+ * version as the reference's loop does (quic/connection.py:1509-1515).  Per
+ * record, on the device, two lanes per connection:
+ *     root     = HMAC-SHA256(salt, cid)            salt = INITIAL_SALT_VERSION_1, or
+ *                                                  _2 with QPP_DERIVE_V2
+ *     secret_x = HKDF-Expand-Label(root, "client in" | "server in", "", 32)
+ *     key(16) / iv(12) / hp(16) of secret_x with the "quic " labels, or the
+ *                                                  "quicv2 " ones with QPP_DERIVE_V2
+ * always as QPP_AES_128_GCM with key_phase 0.  Each direction whose slot is
+ * not QPP_SLOT_NONE is then installed with the same slot expansion as
+ * qpp_keytab_set.  km_out (host memory, may be NULL) receives 2n records:
+ * [2i] the client direction of record i, [2i + 1] its server direction; a
+ * direction given QPP_SLOT_NONE is derived and returned all the same, with
+ * slot = QPP_SLOT_NONE, only not installed.  secrets_out (host memory, may be
+ * NULL) receives the 2n x 32 bytes of the "client in" / "server in" secrets in
+ * the same order (CryptoContext.secret).  km_out feeds qpp_multi_set_keys
+ * unchanged.
+ * QPP_E_ARG, with nothing installed: NULL kt, NULL ini with n > 0, n > 2^24, a
+ * slot that is neither < capacity nor QPP_SLOT_NONE, cid_len > QPP_CID_MAX, a
+ * flag bit other than QPP_DERIVE_V2, or slot_client == slot_server (unless
+ * both are QPP_SLOT_NONE).  The same slot named by two different records is
+ * the caller's race, as with qpp_keytab_set.  n == 0 returns QPP_OK.
+ * Synchronous, like qpp_keytab_derive: the records are caller memory. */
+int qpp_keytab_derive_initial(qpp_keytab *kt, const qpp_initial *ini, uint32_t n,
+                              qpp_key_material *km_out, uint8_t *secrets_out, void *stream);
+/* Where a qpp_keytab_derive_initial call's device time goes (diagnostic, for
+ * tools/bench_initial_keys.py): enable != 0 makes the table's following calls
+ * put timing events around their two kernels (0 off, -1 unchanged); derive_ms
+ * and setup_ms (may be NULL) receive the last timed call's durations of the
+ * derivation kernel and of the slot expansion (0 before any). */
+int qpp_keytab_derive_trace(qpp_keytab *kt, int enable, float *derive_ms, float *setup_ms);
 
 /* Batched packet protection on device buffers (asynchronous on `stream`).
  * qpp_protect replaces AEAD_encrypt (_crypto.c:157-194) + HeaderProtection_apply
