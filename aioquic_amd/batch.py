@@ -122,6 +122,37 @@ class PacketEngine:
         _crypto.unprotect(self.table, _ptr(desc), int(n), _ptr(inbuf), _ptr(outbuf),
                           _ptr(results), self._stream(stream), plan)
 
+    # ------------------------------------------------------- routing ----
+
+    @staticmethod
+    def cid_map(capacity: int):
+        """A device-resident connection-ID map (qpp_cidmap) for up to
+        `capacity` CIDs: .put(records) / .remove(records) of layout.CID_ENTRY
+        bytes, .find(cid), .home(cid), .count, .buckets."""
+        return _crypto.CidMap(int(capacity))
+
+    def route(self, cid_map, cid_len: int, offs, lens, n: int, inbuf, conn_slot, conn_expected, n_conn: int,
+              route, desc=None, flags: int = 0, stream=None) -> None:
+        """qpp_route on device buffers: n raw datagrams (uint64 `offs`, uint32
+        `lens` into `inbuf`) to ROUTE records and, unless `desc` is None,
+        unprotect-ready DESC records, from the per-connection arrays
+        `conn_slot` (uint32) and `conn_expected` (uint64) of n_conn entries."""
+        _crypto.route(cid_map, int(cid_len), _ptr(offs), _ptr(lens), int(n), _ptr(inbuf), _ptr(conn_slot),
+                      _ptr(conn_expected), int(n_conn), int(flags), 0 if desc is None else _ptr(desc), _ptr(route),
+                      self._stream(stream))
+
+    def route_unprotect_host(self, cid_map, cid_len: int, offs, lens, data, conn_slot, conn_expected,
+                             out_len: int, flags: int = 0):
+        """Route and unprotect a host buffer of raw datagrams in one call
+        (qpp_session_route_unprotect).  Returns (out, desc, route, results)."""
+        out, desc, route, res = _crypto.route_unprotect_host(
+            self.table, cid_map, int(cid_len), np.ascontiguousarray(offs, dtype=np.uint64).tobytes(),
+            np.ascontiguousarray(lens, dtype=np.uint32).tobytes(), bytes(data),
+            np.ascontiguousarray(conn_slot, dtype=np.uint32).tobytes(),
+            np.ascontiguousarray(conn_expected, dtype=np.uint64).tobytes(), int(flags), int(out_len))
+        return (np.frombuffer(out, dtype=np.uint8), np.frombuffer(desc, dtype=L.DESC),
+                np.frombuffer(route, dtype=L.ROUTE), np.frombuffer(res, dtype=L.RESULT))
+
     # ----------------------------------------------- host-buffer forms ----
 
     def protect_host(self, desc: np.ndarray, data, out_len: int):

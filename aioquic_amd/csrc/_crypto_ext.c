@@ -29,6 +29,12 @@
  *   hp_mask_host(table, slots, samples) -> bytes
  *   protect_datagrams(...), unprotect_walk(...)     the batched callers' C paths
  *   MultiSession(devices, key_capacity)             one host batch over several GPUs
+ *   CidMap(capacity) .put(records) .remove(records) .find(cid) .home(cid) .count .buckets
+ *   route(map, cid_len, off_ptr, len_ptr, n, in_ptr, slot_ptr, exp_ptr, n_conn, flags,
+ *         desc_ptr, route_ptr, stream)              raw datagrams -> descriptors, by connection ID
+ *   route_unprotect_host(table, map, cid_len, offs, lens, data, conn_slot, conn_expected,
+ *                        flags, out_len) -> (out, desc, route, results)
+ *   receive_routed(...)                             receive.receive_routed's C path
  *
  * Threads: host-buffer calls release the GIL.  Each OS thread gets its own
  * qpp_session (pinned staging + streams; quic_pp.h: a session is single-
@@ -45,7 +51,7 @@
 #include "quic_pp.h"
 
 static PyObject *g_crypto_error;
-static PyObject *g_aead_type, *g_hp_type, *g_kt_type, *g_plan_type, *g_multi_type;
+static PyObject *g_aead_type, *g_hp_type, *g_kt_type, *g_plan_type, *g_multi_type, *g_cidmap_type;
 
 /* ------------------------------------------------------------ sessions -- */
 
@@ -696,6 +702,120 @@ static int as_plan(PyObject *o, qpp_plan **out)
     return 0;
 }
 
+/* -------------------------------------------------------------- CidMap -- */
+
+/* CidMap(capacity): the device-resident connection-ID map of qpp_route
+ * (qpp_cidmap, quic_pp.h).  Records are packed 32-byte qpp_cid_entry. */
+typedef struct {
+    PyObject_HEAD
+    qpp_cidmap *map;
+} CidMapObject;
+
+static int CidMap_init(CidMapObject *self, PyObject *args, PyObject *kwargs)
+{
+    unsigned int cap;
+    if (!PyArg_ParseTuple(args, "I", &cap)) return -1;
+    if (self->map) {
+        qpp_cidmap_destroy(self->map);
+        self->map = NULL;
+    }
+    int rc = qpp_cidmap_create(cap, &self->map);
+    if (rc == QPP_E_ARG) {
+        PyErr_SetString(PyExc_ValueError, "invalid connection-ID map capacity");
+        return -1;
+    }
+    return check_rc(rc);
+}
+
+static void CidMap_dealloc(CidMapObject *self)
+{
+    if (self->map) qpp_cidmap_destroy(self->map);
+    heap_dealloc((PyObject *)self);
+}
+
+static PyObject *cidmap_change(CidMapObject *self, PyObject *args, int put)
+{
+    const char *b;
+    Py_ssize_t len;
+    unsigned long long stream = 0;
+    if (!PyArg_ParseTuple(args, "y#|K", &b, &len, &stream)) return NULL;
+    if (len % (Py_ssize_t)sizeof(qpp_cid_entry)) {
+        PyErr_SetString(PyExc_ValueError, "records must be a whole number of 32-byte entries");
+        return NULL;
+    }
+    const uint32_t n = (uint32_t)(len / (Py_ssize_t)sizeof(qpp_cid_entry));
+    int rc;
+    Py_BEGIN_ALLOW_THREADS
+    rc = (put ? qpp_cidmap_put : qpp_cidmap_remove)(self->map, (const qpp_cid_entry *)b, n, as_ptr(stream));
+    Py_END_ALLOW_THREADS
+    if (rc == QPP_E_ARG) {
+        PyErr_SetString(PyExc_ValueError, put ? "bad entries (a CID length outside 1..20, or more CIDs than the "
+                                                "map's capacity); nothing was changed"
+                                              : "bad entries (a CID length outside 1..20); nothing was changed");
+        return NULL;
+    }
+    if (check_rc(rc) < 0) return NULL;
+    Py_RETURN_NONE;
+}
+
+static PyObject *CidMap_put(CidMapObject *self, PyObject *args) { return cidmap_change(self, args, 1); }
+static PyObject *CidMap_remove(CidMapObject *self, PyObject *args) { return cidmap_change(self, args, 0); }
+
+static PyObject *cidmap_query(CidMapObject *self, PyObject *args, int home)
+{
+    const char *cid;
+    Py_ssize_t len;
+    if (!PyArg_ParseTuple(args, "y#", &cid, &len)) return NULL;
+    if (len < 1 || len > QPP_CID_MAX) {
+        PyErr_SetString(PyExc_ValueError, "connection ID must be 1..20 bytes");
+        return NULL;
+    }
+    const uint32_t v = (home ? qpp_cidmap_home : qpp_cidmap_find)(self->map, (const uint8_t *)cid, (uint32_t)len);
+    if (!home && v == QPP_CONN_NONE) Py_RETURN_NONE;
+    return PyLong_FromUnsignedLong(v);
+}
+
+static PyObject *CidMap_find(CidMapObject *self, PyObject *args) { return cidmap_query(self, args, 0); }
+static PyObject *CidMap_home(CidMapObject *self, PyObject *args) { return cidmap_query(self, args, 1); }
+static PyObject *CidMap_count(CidMapObject *self, void *unused) { return PyLong_FromUnsignedLong(qpp_cidmap_count(self->map)); }
+static PyObject *CidMap_buckets(CidMapObject *self, void *unused) { return PyLong_FromUnsignedLong(qpp_cidmap_buckets(self->map)); }
+
+static PyMethodDef CidMap_methods[] = {
+    {"put", (PyCFunction)CidMap_put, METH_VARARGS, "put(records, stream=0): add CIDs or replace their connection"},
+    {"remove", (PyCFunction)CidMap_remove, METH_VARARGS, "remove(records, stream=0): retire CIDs (absent ones are ignored)"},
+    {"find", (PyCFunction)CidMap_find, METH_VARARGS, "find(cid) -> connection index or None (the host mirror)"},
+    {"home", (PyCFunction)CidMap_home, METH_VARARGS, "home(cid) -> the CID's home bucket (diagnostic)"},
+    {NULL},
+};
+
+static PyGetSetDef CidMap_getset[] = {
+    {"count", (getter)CidMap_count, NULL, "CIDs in the map", NULL},
+    {"buckets", (getter)CidMap_buckets, NULL, "buckets of the table", NULL},
+    {NULL},
+};
+
+static PyType_Slot CidMap_slots[] = {
+    {Py_tp_doc, "device-resident connection-ID map"},
+    {Py_tp_methods, CidMap_methods},
+    {Py_tp_getset, CidMap_getset},
+    {Py_tp_init, CidMap_init},
+    {Py_tp_new, PyType_GenericNew},
+    {Py_tp_dealloc, CidMap_dealloc},
+    {0, NULL},
+};
+
+static PyType_Spec CidMap_spec = {"aioquic_amd._crypto.CidMap", sizeof(CidMapObject), 0,
+                                  Py_TPFLAGS_DEFAULT, CidMap_slots};
+
+static qpp_cidmap *as_cidmap(PyObject *o)
+{
+    if (!PyObject_TypeCheck(o, (PyTypeObject *)g_cidmap_type)) {
+        PyErr_SetString(PyExc_TypeError, "expected a CidMap");
+        return NULL;
+    }
+    return ((CidMapObject *)o)->map;
+}
+
 /* --------------------------------------------------------- MultiSession -- */
 
 /* MultiSession(devices, key_capacity): one host batch over several GPUs
@@ -936,6 +1056,84 @@ static PyObject *py_plan_build(PyObject *m, PyObject *args)
     }
     if (check_rc(rc) < 0) return NULL;
     Py_RETURN_NONE;
+}
+
+/* route(map, cid_len, off_ptr, len_ptr, n, in_ptr, slot_ptr, exp_ptr, n_conn, flags, desc_ptr, route_ptr, stream) */
+static PyObject *py_route(PyObject *m, PyObject *args)
+{
+    PyObject *mo;
+    unsigned long long op, lp, ip, slp, ep, dp, rp, sp;
+    unsigned int cid_len, n, n_conn, flags;
+    if (!PyArg_ParseTuple(args, "OIKKIKKKIIKKK", &mo, &cid_len, &op, &lp, &n, &ip, &slp, &ep, &n_conn, &flags, &dp,
+                          &rp, &sp))
+        return NULL;
+    qpp_cidmap *map = as_cidmap(mo);
+    if (!map) return NULL;
+    if (flags > 0xffff) {
+        PyErr_SetString(PyExc_ValueError, "descriptor flags are 16 bits");
+        return NULL;
+    }
+    int rc = qpp_route(map, cid_len, as_ptr(op), as_ptr(lp), n, as_ptr(ip), as_ptr(slp), as_ptr(ep), n_conn,
+                       (uint16_t)flags, as_ptr(dp), as_ptr(rp), as_ptr(sp));
+    if (rc == QPP_E_ARG) {
+        PyErr_SetString(PyExc_ValueError, "bad route arguments (cid_len outside 1..20, or a null buffer)");
+        return NULL;
+    }
+    if (check_rc(rc) < 0) return NULL;
+    Py_RETURN_NONE;
+}
+
+/* route_unprotect_host(table, map, cid_len, offs_u64, lens_u32, data, conn_slot_u32, conn_expected_u64,
+ *                      flags, out_len) -> (out, desc, route, results) */
+static PyObject *py_route_unprotect_host(PyObject *m, PyObject *args)
+{
+    PyObject *t, *mo;
+    const char *offs, *lens, *data, *cslot, *cexp;
+    Py_ssize_t l_offs, l_lens, l_data, l_cslot, l_cexp, out_len;
+    unsigned int cid_len, flags;
+    if (!PyArg_ParseTuple(args, "OOIy#y#y#y#y#In", &t, &mo, &cid_len, &offs, &l_offs, &lens, &l_lens, &data, &l_data,
+                          &cslot, &l_cslot, &cexp, &l_cexp, &flags, &out_len))
+        return NULL;
+    qpp_keytab *kt = as_table(t);
+    qpp_cidmap *map = kt ? as_cidmap(mo) : NULL;
+    if (!map) return NULL;
+    const Py_ssize_t n = l_lens / 4, nc = l_cslot / 4;
+    if (l_lens % 4 || l_cslot % 4 || l_offs != n * 8 || l_cexp != nc * 8 || out_len < 0 || flags > 0xffff ||
+        n > 0x7fffffff || nc > 0x7fffffff) {
+        PyErr_SetString(PyExc_ValueError, "bad array lengths, flags or output length");
+        return NULL;
+    }
+    PyObject *out = PyBytes_FromStringAndSize(NULL, out_len);
+    PyObject *desc = PyBytes_FromStringAndSize(NULL, n * (Py_ssize_t)sizeof(qpp_desc));
+    PyObject *route = PyBytes_FromStringAndSize(NULL, n * (Py_ssize_t)sizeof(qpp_route_rec));
+    PyObject *res = PyBytes_FromStringAndSize(NULL, n * (Py_ssize_t)sizeof(qpp_result));
+    PyObject *ret = NULL;
+    qpp_session *s = out && desc && route && res ? session() : NULL;
+    if (s) {
+        char *o = PyBytes_AsString(out);
+        /* an empty batch, or a refused one, leaves `out` as zeros */
+        memset(o, 0, (size_t)out_len);
+        int rc;
+        Py_BEGIN_ALLOW_THREADS
+        rc = qpp_session_route_unprotect(s, kt, map, cid_len, (const uint64_t *)offs, (const uint32_t *)lens,
+                                         (uint32_t)n, (const uint8_t *)data, (size_t)l_data,
+                                         (const uint32_t *)cslot, (const uint64_t *)cexp, (uint32_t)nc,
+                                         (uint16_t)flags, (uint8_t *)o, (size_t)out_len,
+                                         (qpp_desc *)PyBytes_AsString(desc),
+                                         (qpp_route_rec *)PyBytes_AsString(route),
+                                         (qpp_result *)PyBytes_AsString(res));
+        Py_END_ALLOW_THREADS
+        if (rc == QPP_E_ARG)
+            PyErr_SetString(PyExc_ValueError, "bad route arguments (cid_len outside 1..20, or a datagram outside "
+                                              "the input or the output buffer); nothing was launched");
+        else if (check_rc(rc) == 0)
+            ret = PyTuple_Pack(4, out, desc, route, res);
+    }
+    Py_XDECREF(out);
+    Py_XDECREF(desc);
+    Py_XDECREF(route);
+    Py_XDECREF(res);
+    return ret;
 }
 
 static int host_call(int enc, qpp_keytab *kt, const void *desc, uint32_t n, const void *in,
@@ -1585,6 +1783,137 @@ static PyObject *make_record(PyTypeObject *tp, allocfunc alloc, PyObject *const 
     return r;
 }
 
+/* The in-order walk after the launch of receive_short / receive_routed:
+ * CryptoPair.decrypt_packet's sequential semantics (quic/crypto.py:184-192)
+ * over the records of one batch, one ReceivedPacket per record or None and an
+ * entry in `deferred` (the record's position) for the caller's general path.
+ * Record j is datagram dg[j] (NULL: j itself) of connection conn_of[j];
+ * slot_of[j] >= RS_CLOSED means nothing was launched for it; otherwise its
+ * descriptor and result are desc / res [rix[j]], or, with rix NULL, the next
+ * of the launched ones in order. */
+typedef struct {
+    Py_ssize_t n;
+    const uint32_t *dg, *rix;
+    const uint32_t *conn_of, *slot_of, *cpair, *cspace;
+    const qpp_desc *desc;
+    const qpp_result *res;
+    const uint8_t *hout;
+    uint64_t *sx;     /* expected packet number per space, updated */
+    uint8_t *closed;  /* per connection, updated */
+    uint8_t *blocked_pair, *blocked_space, *blocked_conn;
+    PyObject *recs, *deferred;
+    PyTypeObject *tp;
+    allocfunc alloc;
+    PyObject *ptype, *epoch, *empty, *minus1, *zero, *s_key, *s_dec, *s_rsv, *s_closed;
+    /* output copies: header and payload of every packet, for the caller's par_copy */
+    uint8_t **od;
+    const uint8_t **os_;
+    size_t *ol, on, otot;
+} ShortWalk;
+
+static int short_walk(ShortWalk *w)
+{
+    const Py_ssize_t n = w->n;
+    const uint32_t *conn_of = w->conn_of, *slot_of = w->slot_of, *cpair = w->cpair, *cspace = w->cspace;
+    const qpp_desc *desc = w->desc;
+    const uint8_t *hout = w->hout;
+    uint8_t *blocked_pair = w->blocked_pair, *blocked_space = w->blocked_space, *blocked_conn = w->blocked_conn;
+    PyObject *recs = w->recs, *deferred = w->deferred, *ptype = w->ptype, *epoch = w->epoch, *empty = w->empty;
+    PyObject *minus1 = w->minus1, *zero = w->zero, *s_key = w->s_key, *s_dec = w->s_dec, *s_rsv = w->s_rsv;
+    PyObject *s_closed = w->s_closed;
+    PyTypeObject *tp = w->tp;
+    allocfunc alloc = w->alloc;
+    uint8_t **od = w->od;
+    const uint8_t **os_ = w->os_;
+    size_t *ol = w->ol, on = w->on, otot = w->otot;
+    int rc = -1;
+    {
+        uint64_t *sx = w->sx;
+        uint8_t *closed = w->closed;
+        const qpp_result *r = w->res;
+        uint32_t k = 0;
+        for (Py_ssize_t i = 0; i < n; ++i) {
+            PyObject *di = PyLong_FromSsize_t(w->dg ? (Py_ssize_t)w->dg[i] : i);
+            if (!di) goto done;
+            const uint32_t c = conn_of[i], p = cpair[c], sp = cspace[c];
+            const int launched = slot_of[i] < RS_CLOSED;
+            const uint32_t x = w->rix ? w->rix[i] : k;
+            const qpp_result *ri = launched ? &r[x] : NULL;
+            const qpp_desc *dk = launched ? &desc[x] : NULL;
+            k += launched;
+            /* a deferred packet of the connection may close it: wait for it */
+            int defer = blocked_conn[c];
+            if (!defer && launched) {
+                const uint64_t now = sx[sp];
+                defer = blocked_pair[p] || blocked_space[sp] || (!closed[c] && ri->status == QPP_S_KEY_PHASE);
+                if (!defer && !closed[c] && now != dk->pn && (ri->status == QPP_S_OK || ri->status == QPP_S_DECRYPT)) {
+                    const int pn_len = (int)ri->hdr_len - (int)dk->hdr_len;
+                    if (pn_len < 1 || pn_len > 4 || decode_pn_signed(ri->pn, pn_len, now) != (int64_t)ri->pn)
+                        defer = 1;
+                }
+            }
+            if (defer) {
+                blocked_conn[c] = 1;
+                if (launched) blocked_pair[p] = blocked_space[sp] = 1;
+                PyObject *dj = w->dg ? PyLong_FromSsize_t(i) : di;
+                const int bad = dj ? PyList_Append(deferred, dj) : -1;
+                if (w->dg) Py_XDECREF(dj);
+                Py_INCREF(Py_None);
+                PyList_SetItem(recs, i, Py_None);
+                Py_DECREF(di);
+                if (bad < 0) goto done;
+                continue;
+            }
+            PyObject *rec = NULL;
+            if (closed[c]) {
+                /* connection.py:756-757 */
+                PyObject *f[9] = {di, zero, Py_None, ptype, Py_None, empty, empty, minus1, s_closed};
+                rec = make_record(tp, alloc, f, 9);
+            } else if (!launched) {
+                PyObject *f[9] = {di, zero, Py_None, ptype, epoch, empty, empty, minus1, s_key};
+                rec = make_record(tp, alloc, f, 9);
+            } else {
+                const uint64_t now = sx[sp];
+                if (ri->status == QPP_S_OK && (hout[dk->out_off] & 0x18)) {
+                    /* connection.py:949-960: the close, before :984-985 */
+                    closed[c] = 1;
+                    PyObject *f[9] = {di, zero, Py_None, ptype, epoch, empty, empty, minus1, s_rsv};
+                    rec = make_record(tp, alloc, f, 9);
+                } else if (ri->status == QPP_S_OK) {
+                    const uint8_t *o = hout + dk->out_off;
+                    const size_t pll = (size_t)ri->out_len - ri->hdr_len;
+                    PyObject *h = PyBytes_FromStringAndSize(NULL, ri->hdr_len);
+                    PyObject *pl = PyBytes_FromStringAndSize(NULL, (Py_ssize_t)pll);
+                    PyObject *pn = PyLong_FromUnsignedLongLong(ri->pn);
+                    if (h && pl && pn) {
+                        od[on] = (uint8_t *)PyBytes_AsString(h), os_[on] = o, ol[on++] = ri->hdr_len;
+                        od[on] = (uint8_t *)PyBytes_AsString(pl), os_[on] = o + ri->hdr_len, ol[on++] = pll;
+                        otot += ri->hdr_len + pll;
+                        PyObject *f[9] = {di, zero, Py_None, ptype, epoch, h, pl, pn, Py_None};
+                        rec = make_record(tp, alloc, f, 9);
+                    }
+                    Py_XDECREF(h);
+                    Py_XDECREF(pl);
+                    Py_XDECREF(pn);
+                    if (ri->pn > now) sx[sp] = ri->pn + 1;
+                } else {
+                    PyObject *f[9] = {di, zero, Py_None, ptype, epoch, empty, empty, minus1,
+                                      ri->status == QPP_S_NO_KEY ? s_key : s_dec};
+                    rec = make_record(tp, alloc, f, 9);
+                }
+            }
+            Py_DECREF(di);
+            if (!rec) goto done;
+            PyList_SetItem(recs, i, rec);
+        }
+    }
+    rc = 0;
+done:
+    w->on = on;
+    w->otot = otot;
+    return rc;
+}
+
 /* receive_short(table, items, conns, conn_cid_u32, conn_pair_u32,
  *               conn_space_u32, pair_slot_u32, space_exp_u64, rec_type,
  *               packet_type, epoch, conn_closed_u8)
@@ -1730,81 +2059,13 @@ static PyObject *py_receive_short(PyObject *m, PyObject *args)
         if (host_call(0, kt, desc, nl, hin, total, hout, total, PyBytes_AsString(res)) < 0) goto done;
     }
     {
-        uint64_t *sx = (uint64_t *)PyBytes_AsString(sexp_out);
-        uint8_t *closed = (uint8_t *)PyBytes_AsString(closed_out);
-        const qpp_result *r = (const qpp_result *)PyBytes_AsString(res);
-        uint32_t k = 0;
-        for (Py_ssize_t i = 0; i < n; ++i) {
-            PyObject *di = PyLong_FromSsize_t(i);
-            if (!di) goto done;
-            const uint32_t c = conn_of[i], p = cpair[c], sp = cspace[c];
-            const int launched = slot_of[i] < RS_CLOSED;
-            const qpp_result *ri = launched ? &r[k] : NULL;
-            const qpp_desc *dk = launched ? &desc[k] : NULL;
-            k += launched;
-            /* a deferred packet of the connection may close it: wait for it */
-            int defer = blocked_conn[c];
-            if (!defer && launched) {
-                const uint64_t now = sx[sp];
-                defer = blocked_pair[p] || blocked_space[sp] || (!closed[c] && ri->status == QPP_S_KEY_PHASE);
-                if (!defer && !closed[c] && now != dk->pn && (ri->status == QPP_S_OK || ri->status == QPP_S_DECRYPT)) {
-                    const int pn_len = (int)ri->hdr_len - (int)dk->hdr_len;
-                    if (pn_len < 1 || pn_len > 4 || decode_pn_signed(ri->pn, pn_len, now) != (int64_t)ri->pn)
-                        defer = 1;
-                }
-            }
-            if (defer) {
-                blocked_conn[c] = 1;
-                if (launched) blocked_pair[p] = blocked_space[sp] = 1;
-                const int bad = PyList_Append(deferred, di);
-                Py_INCREF(Py_None);
-                PyList_SetItem(recs, i, Py_None);
-                Py_DECREF(di);
-                if (bad < 0) goto done;
-                continue;
-            }
-            PyObject *rec = NULL;
-            if (closed[c]) {
-                /* connection.py:756-757 */
-                PyObject *f[9] = {di, zero, Py_None, ptype, Py_None, empty, empty, minus1, s_closed};
-                rec = make_record(tp, alloc, f, 9);
-            } else if (!launched) {
-                PyObject *f[9] = {di, zero, Py_None, ptype, epoch, empty, empty, minus1, s_key};
-                rec = make_record(tp, alloc, f, 9);
-            } else {
-                const uint64_t now = sx[sp];
-                if (ri->status == QPP_S_OK && (hout[dk->out_off] & 0x18)) {
-                    /* connection.py:949-960: the close, before :984-985 */
-                    closed[c] = 1;
-                    PyObject *f[9] = {di, zero, Py_None, ptype, epoch, empty, empty, minus1, s_rsv};
-                    rec = make_record(tp, alloc, f, 9);
-                } else if (ri->status == QPP_S_OK) {
-                    const uint8_t *o = hout + dk->out_off;
-                    const size_t pll = (size_t)ri->out_len - ri->hdr_len;
-                    PyObject *h = PyBytes_FromStringAndSize(NULL, ri->hdr_len);
-                    PyObject *pl = PyBytes_FromStringAndSize(NULL, (Py_ssize_t)pll);
-                    PyObject *pn = PyLong_FromUnsignedLongLong(ri->pn);
-                    if (h && pl && pn) {
-                        od[on] = (uint8_t *)PyBytes_AsString(h), os_[on] = o, ol[on++] = ri->hdr_len;
-                        od[on] = (uint8_t *)PyBytes_AsString(pl), os_[on] = o + ri->hdr_len, ol[on++] = pll;
-                        otot += ri->hdr_len + pll;
-                        PyObject *f[9] = {di, zero, Py_None, ptype, epoch, h, pl, pn, Py_None};
-                        rec = make_record(tp, alloc, f, 9);
-                    }
-                    Py_XDECREF(h);
-                    Py_XDECREF(pl);
-                    Py_XDECREF(pn);
-                    if (ri->pn > now) sx[sp] = ri->pn + 1;
-                } else {
-                    PyObject *f[9] = {di, zero, Py_None, ptype, epoch, empty, empty, minus1,
-                                      ri->status == QPP_S_NO_KEY ? s_key : s_dec};
-                    rec = make_record(tp, alloc, f, 9);
-                }
-            }
-            Py_DECREF(di);
-            if (!rec) goto done;
-            PyList_SetItem(recs, i, rec);
-        }
+        ShortWalk w = {n, NULL, NULL, conn_of, slot_of, cpair, cspace, desc, (const qpp_result *)PyBytes_AsString(res),
+                       hout, (uint64_t *)PyBytes_AsString(sexp_out), (uint8_t *)PyBytes_AsString(closed_out),
+                       blocked_pair, blocked_space, blocked_conn, recs, deferred, tp, alloc, ptype, epoch, empty,
+                       minus1, zero, s_key, s_dec, s_rsv, s_closed, od, os_, ol, 0, 0};
+        if (short_walk(&w) < 0) goto done;
+        on = w.on;
+        otot = w.otot;
     }
     Py_BEGIN_ALLOW_THREADS
     par_copy(od, os_, ol, on, otot);
@@ -1834,6 +2095,190 @@ done:
     Py_XDECREF(minus1);
     Py_XDECREF(s_key);
     Py_XDECREF(s_dec);
+    return ret;
+}
+
+/* receive_routed(table, map, cid_len, datagrams, conn_pair_u32, conn_space_u32,
+ *                pair_slot_u32, space_exp_u64, rec_type, packet_type, epoch,
+ *                conn_closed_u8, walk)
+ *     -> (route, None) | (route, (records, deferred, space_exp after, conn_closed after))
+ * receive_short for datagrams nobody has demultiplexed: `datagrams` is a list
+ * of bytes, and the connection of each comes from the route records of one
+ * qpp_session_route_unprotect call over the staged batch (its routing kernel
+ * fills in every descriptor's slot and expected packet number from the
+ * per-connection arrays built here: a closed or keyless connection gets
+ * QPP_SLOT_NONE, and the walk tells them apart by the closed flags).  Then
+ * the same in-order walk as receive_short, over the QPP_R_SHORT datagrams
+ * only: records[j] is the j-th of them, its .datagram the caller's index;
+ * `deferred` holds positions j.  `route` is the batch's packed qpp_route_rec.
+ * No walk (None, nothing of the state consulted again) with walk == 0 or when
+ * a long-header datagram belongs to a known connection: the caller's general
+ * path takes the batch then. */
+static PyObject *py_receive_routed(PyObject *m, PyObject *args)
+{
+    PyObject *t, *mo, *dgs, *rec_type, *ptype, *epoch;
+    const char *a_pair, *a_space, *a_pslot, *a_sexp, *a_closed;
+    Py_ssize_t l_pair, l_space, l_pslot, l_sexp, l_closed;
+    unsigned int cid_len;
+    int walk;
+    if (!PyArg_ParseTuple(args, "OOIO!y#y#y#y#OOOy#i", &t, &mo, &cid_len, &PyList_Type, &dgs, &a_pair, &l_pair,
+                          &a_space, &l_space, &a_pslot, &l_pslot, &a_sexp, &l_sexp, &rec_type, &ptype, &epoch,
+                          &a_closed, &l_closed, &walk))
+        return NULL;
+    qpp_keytab *kt = as_table(t);
+    qpp_cidmap *map = kt ? as_cidmap(mo) : NULL;
+    if (!map) return NULL;
+    if (!PyType_Check(rec_type) || !PyType_IsSubtype((PyTypeObject *)rec_type, &PyTuple_Type)) {
+        PyErr_SetString(PyExc_TypeError, "rec_type must be a tuple subclass");
+        return NULL;
+    }
+    if (cid_len < 1 || cid_len > QPP_CID_MAX) {
+        PyErr_SetString(PyExc_ValueError, "cid_len must be 1..20");
+        return NULL;
+    }
+    const Py_ssize_t n = PyList_Size(dgs), nc = l_closed;
+    const Py_ssize_t n_pairs = l_pslot / 4, n_spaces = l_sexp / 8;
+    if (check_len(l_pair, nc, 4, "conn_pair") < 0 || check_len(l_space, nc, 4, "conn_space") < 0) return NULL;
+    const uint32_t *cpair = (const uint32_t *)a_pair, *cspace = (const uint32_t *)a_space,
+                   *pslot = (const uint32_t *)a_pslot;
+    for (Py_ssize_t c = 0; c < nc; ++c)
+        if ((Py_ssize_t)cpair[c] >= n_pairs || (Py_ssize_t)cspace[c] >= n_spaces) {
+            PyErr_SetString(PyExc_ValueError, "pair or space index out of range");
+            return NULL;
+        }
+    if (n > 0x7fffffff || nc > 0x7fffffff) {
+        PyErr_SetString(PyExc_ValueError, "batch too large");
+        return NULL;
+    }
+    PyTypeObject *tp = (PyTypeObject *)rec_type;
+    allocfunc alloc = (allocfunc)PyType_GetSlot(tp, Py_tp_alloc);
+    if (!alloc) return NULL;
+    /* a snapshot holding a reference to every datagram: the copies below run without the GIL */
+    dgs = PySequence_Tuple(dgs);
+    if (!dgs) return NULL;
+
+    const size_t n1 = n ? (size_t)n : 1, nc1 = nc ? (size_t)nc : 1;
+    uint64_t *offs = (uint64_t *)malloc(n1 * sizeof(uint64_t)), *cexp = (uint64_t *)malloc(nc1 * sizeof(uint64_t));
+    uint32_t *lens = (uint32_t *)malloc(n1 * sizeof(uint32_t)), *cslot = (uint32_t *)malloc(nc1 * sizeof(uint32_t));
+    uint32_t *conn_of = (uint32_t *)malloc(n1 * sizeof(uint32_t)), *slot_of = (uint32_t *)malloc(n1 * sizeof(uint32_t));
+    uint32_t *dg = (uint32_t *)malloc(n1 * sizeof(uint32_t));
+    qpp_desc *desc = (qpp_desc *)malloc(n1 * sizeof(qpp_desc));
+    qpp_result *res = (qpp_result *)malloc(n1 * sizeof(qpp_result));
+    uint8_t **cd = (uint8_t **)malloc(n1 * sizeof(uint8_t *));
+    const uint8_t **cs = (const uint8_t **)malloc(n1 * sizeof(uint8_t *));
+    size_t *cl = (size_t *)malloc(n1 * sizeof(size_t));
+    uint8_t *blocked_pair = (uint8_t *)calloc(n_pairs ? (size_t)n_pairs : 1, 1);
+    uint8_t *blocked_space = (uint8_t *)calloc(n_spaces ? (size_t)n_spaces : 1, 1);
+    uint8_t *blocked_conn = (uint8_t *)calloc(nc1, 1);
+    uint8_t **od = (uint8_t **)malloc((2 * (size_t)n + 1) * sizeof(uint8_t *));
+    const uint8_t **os_ = (const uint8_t **)malloc((2 * (size_t)n + 1) * sizeof(uint8_t *));
+    size_t *ol = (size_t *)malloc((2 * (size_t)n + 1) * sizeof(size_t));
+    PyObject *ret = NULL, *route = NULL, *recs = NULL, *deferred = NULL, *sexp_out = NULL, *closed_out = NULL;
+    PyObject *empty = NULL, *minus1 = NULL, *zero = NULL, *s_key = NULL, *s_dec = NULL, *s_rsv = NULL, *s_closed = NULL;
+    PyObject *walked = NULL;
+    if (!offs || !cexp || !lens || !cslot || !conn_of || !slot_of || !dg || !desc || !res || !cd || !cs || !cl ||
+        !blocked_pair || !blocked_space || !blocked_conn || !od || !os_ || !ol)
+        goto nomem;
+    size_t total = 0;
+    for (Py_ssize_t i = 0; i < n; ++i) {
+        PyObject *d = PyTuple_GetItem(dgs, i);
+        if (!d || !PyBytes_Check(d)) {
+            PyErr_SetString(PyExc_TypeError, "datagrams must be bytes");
+            goto done;
+        }
+        const Py_ssize_t len = PyBytes_Size(d);
+        if ((uint64_t)len > 0xffffffffu) {
+            PyErr_SetString(PyExc_ValueError, "datagram too long");
+            goto done;
+        }
+        offs[i] = total;
+        lens[i] = (uint32_t)len;
+        cs[i] = (const uint8_t *)PyBytes_AsString(d);
+        cl[i] = (size_t)len;
+        total += (size_t)len;
+    }
+    for (Py_ssize_t c = 0; c < nc; ++c) {
+        cslot[c] = ((const uint8_t *)a_closed)[c] ? QPP_SLOT_NONE : pslot[cpair[c]];
+        cexp[c] = ((const uint64_t *)a_sexp)[cspace[c]];
+    }
+    route = PyBytes_FromStringAndSize(NULL, n * (Py_ssize_t)sizeof(qpp_route_rec));
+    if (!route) goto done;
+    const qpp_route_rec *rr = (const qpp_route_rec *)PyBytes_AsString(route);
+    uint8_t *hin = NULL, *hout = NULL;
+    if (n) {
+        qpp_session *ss = session();
+        if (!ss || check_rc(qpp_session_stage(ss, total ? total : 1, (uint32_t)n, &hin, &hout)) < 0) goto done;
+        for (Py_ssize_t i = 0; i < n; ++i) cd[i] = hin + offs[i];
+        int rc;
+        Py_BEGIN_ALLOW_THREADS  /* the snapshot holds every datagram */
+        par_copy(cd, cs, cl, (size_t)n, total);
+        rc = qpp_session_route_unprotect(ss, kt, map, cid_len, offs, lens, (uint32_t)n, hin, total, cslot, cexp,
+                                         (uint32_t)nc, 0, hout, total, desc, (qpp_route_rec *)rr, res);
+        Py_END_ALLOW_THREADS
+        if (check_rc(rc) < 0) goto done;
+    }
+    /* the records to walk: the short-header datagrams of known connections */
+    Py_ssize_t nr = 0;
+    for (Py_ssize_t i = 0; i < n && walk; ++i) {
+        if (rr[i].cls == QPP_R_LONG && rr[i].conn != QPP_CONN_NONE) walk = 0;
+        if (rr[i].cls != QPP_R_SHORT) continue;
+        const uint32_t c = rr[i].conn;  /* < nc: the kernel checked it */
+        dg[nr] = (uint32_t)i;
+        conn_of[nr] = c;
+        slot_of[nr] = ((const uint8_t *)a_closed)[c] ? RS_CLOSED : cslot[c];
+        ++nr;
+    }
+    if (!walk) {
+        ret = PyTuple_Pack(2, route, Py_None);
+        goto done;
+    }
+    sexp_out = PyBytes_FromStringAndSize(a_sexp, l_sexp);
+    closed_out = PyBytes_FromStringAndSize(a_closed, l_closed);
+    recs = PyList_New(nr);
+    deferred = PyList_New(0);
+    empty = PyBytes_FromStringAndSize("", 0);
+    minus1 = PyLong_FromLong(-1);
+    zero = PyLong_FromLong(0);
+    s_key = PyUnicode_FromString("key_unavailable");
+    s_dec = PyUnicode_FromString("payload_decrypt_error");
+    s_rsv = PyUnicode_FromString("reserved_bits");
+    s_closed = PyUnicode_FromString("connection_closed");
+    if (!sexp_out || !closed_out || !recs || !deferred || !empty || !minus1 || !zero || !s_key || !s_dec || !s_rsv ||
+        !s_closed)
+        goto nomem;
+    {
+        ShortWalk w = {nr, dg, dg, conn_of, slot_of, cpair, cspace, desc, res,
+                       hout, (uint64_t *)PyBytes_AsString(sexp_out), (uint8_t *)PyBytes_AsString(closed_out),
+                       blocked_pair, blocked_space, blocked_conn, recs, deferred, tp, alloc, ptype, epoch, empty,
+                       minus1, zero, s_key, s_dec, s_rsv, s_closed, od, os_, ol, 0, 0};
+        if (short_walk(&w) < 0) goto done;
+        Py_BEGIN_ALLOW_THREADS
+        par_copy(od, os_, ol, w.on, w.otot);
+        Py_END_ALLOW_THREADS
+    }
+    walked = PyTuple_Pack(4, recs, deferred, sexp_out, closed_out);
+    if (walked) ret = PyTuple_Pack(2, route, walked);
+    goto done;
+nomem:
+    PyErr_NoMemory();
+done:
+    free(offs), free(cexp), free(lens), free(cslot), free(conn_of), free(slot_of), free(dg), free(desc), free(res);
+    free(cd), free(cs), free(cl), free(blocked_pair), free(blocked_space), free(blocked_conn), free(od), free(os_);
+    free(ol);
+    Py_DECREF(dgs);
+    Py_XDECREF(route);
+    Py_XDECREF(walked);
+    Py_XDECREF(recs);
+    Py_XDECREF(deferred);
+    Py_XDECREF(sexp_out);
+    Py_XDECREF(closed_out);
+    Py_XDECREF(empty);
+    Py_XDECREF(minus1);
+    Py_XDECREF(zero);
+    Py_XDECREF(s_key);
+    Py_XDECREF(s_dec);
+    Py_XDECREF(s_rsv);
+    Py_XDECREF(s_closed);
     return ret;
 }
 
@@ -1928,6 +2373,14 @@ static PyMethodDef module_methods[] = {
     {"receive_short", py_receive_short, METH_VARARGS,
      "receive_short(table, items, conns, conn_cid_u32, conn_pair_u32, conn_space_u32, pair_slot_u32, space_exp_u64, "
      "rec_type, packet_type, epoch) -> None | (records, deferred, space_exp)"},
+    {"route", py_route, METH_VARARGS,
+     "route(map, cid_len, off_ptr, len_ptr, n, in_ptr, slot_ptr, exp_ptr, n_conn, flags, desc_ptr, route_ptr, stream)"},
+    {"route_unprotect_host", py_route_unprotect_host, METH_VARARGS,
+     "route_unprotect_host(table, map, cid_len, offs_u64, lens_u32, data, conn_slot_u32, conn_expected_u64, flags, "
+     "out_len) -> (out, desc, route, results)"},
+    {"receive_routed", py_receive_routed, METH_VARARGS,
+     "receive_routed(table, map, cid_len, datagrams, conn_pair_u32, conn_space_u32, pair_slot_u32, space_exp_u64, "
+     "rec_type, packet_type, epoch, conn_closed_u8, walk) -> (route, None | (records, deferred, space_exp, closed))"},
     {"hp_mask_host", py_hp_mask_host, METH_VARARGS, "hp_mask_host(table, slots_u32, samples) -> masks"},
     {"device_ok", py_device_ok, METH_NOARGS, "True when a gfx950 device is usable"},
     {"abi_version", py_abi, METH_NOARGS, "C ABI version of libquicpp"},
@@ -1993,10 +2446,13 @@ PyMODINIT_FUNC PyInit__crypto(void)
         add_type(m, &HP_spec, "HeaderProtection", &g_hp_type) < 0 ||
         add_type(m, &KT_spec, "KeyTable", &g_kt_type) < 0 ||
         add_type(m, &Plan_spec, "Plan", &g_plan_type) < 0 ||
-        add_type(m, &Multi_spec, "MultiSession", &g_multi_type) < 0)
+        add_type(m, &Multi_spec, "MultiSession", &g_multi_type) < 0 ||
+        add_type(m, &CidMap_spec, "CidMap", &g_cidmap_type) < 0)
         return NULL;
     PyModule_AddIntConstant(m, "DESC_SIZE", (long)sizeof(qpp_desc));
     PyModule_AddIntConstant(m, "RESULT_SIZE", (long)sizeof(qpp_result));
     PyModule_AddIntConstant(m, "KEY_MATERIAL_SIZE", (long)sizeof(qpp_key_material));
+    PyModule_AddIntConstant(m, "CID_ENTRY_SIZE", (long)sizeof(qpp_cid_entry));
+    PyModule_AddIntConstant(m, "ROUTE_SIZE", (long)sizeof(qpp_route_rec));
     return m;
 }

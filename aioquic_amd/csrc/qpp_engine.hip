@@ -3001,6 +3001,10 @@ struct qpp_session {
     bool trace;
     hipEvent_t tev[6][kPipeMaxChunks];
     qpp_trace last;
+    // qpp_session_route_unprotect (qpp_route.hip): the small arrays of a routed
+    // batch, apart from the staging above, which a caller may have filled
+    uint8_t *h_scratch, *d_scratch;  // pinned / device
+    size_t scratch_bytes;
 };
 
 // Host batches of at least this many packets are bucketed by (suite, slot)
@@ -3701,6 +3705,8 @@ void qpp_session_destroy(qpp_session *s)
     if (s->s_in) (void)hipStreamSynchronize(s->s_in);
     if (s->s_out) (void)hipStreamSynchronize(s->s_out);
     session_free_buffers(s);
+    if (s->h_scratch) (void)hipHostFree(s->h_scratch);
+    if (s->d_scratch) (void)hipFree(s->d_scratch);
     qpp_plan_destroy(s->plan);
     for (int c = 0; c < kPipeMaxChunks; ++c) {
         if (s->ev_in[c]) (void)hipEventDestroy(s->ev_in[c]);
@@ -4329,6 +4335,37 @@ int qpp_session_stage(qpp_session *s, size_t bytes, uint32_t n, uint8_t **h_in, 
     *h_out = s->h_out;
     return QPP_OK;
 }
+
+}  // extern "C"
+
+// The session's staging, sized as by qpp_session_stage, and `scratch` bytes of
+// pinned and device scratch beside it (qpp_internal.h).
+int qpp_internal_session_bufs(qpp_session *s, size_t bytes, uint32_t packets, size_t scratch,
+                              qpp_session_bufs *out)
+{
+    if (!s || !out) return QPP_E_ARG;
+    const int rc = session_reserve(s, bytes, packets);
+    if (rc != QPP_OK) return rc;
+    if (scratch > s->scratch_bytes) {
+        HIPCHK(hipStreamSynchronize(s->stream));
+        if (s->h_scratch) (void)hipHostFree(s->h_scratch);
+        if (s->d_scratch) (void)hipFree(s->d_scratch);
+        s->h_scratch = s->d_scratch = NULL;
+        s->scratch_bytes = 0;
+        if (hipHostMalloc(&s->h_scratch, scratch, hipHostMallocDefault) != hipSuccess ||
+            hipMalloc(&s->d_scratch, scratch) != hipSuccess) {
+            (void)hipGetLastError();
+            if (s->h_scratch) (void)hipHostFree(s->h_scratch);
+            s->h_scratch = NULL;
+            return QPP_E_NOMEM;
+        }
+        s->scratch_bytes = scratch;
+    }
+    *out = qpp_session_bufs{s->stream, s->h_in, s->h_out, s->d_in, s->d_out, s->h_scratch, s->d_scratch};
+    return QPP_OK;
+}
+
+extern "C" {
 
 int qpp_session_hp_mask(qpp_session *s, const qpp_keytab *kt, const uint32_t *slots,
                         const uint8_t *samples, uint32_t n, uint8_t *masks)

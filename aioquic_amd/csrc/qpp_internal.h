@@ -43,3 +43,16 @@ int qpp_internal_plan_gather(const qpp_plan *p, const qpp_desc *d_desc, uint32_t
 // wave items of a batch of n packets on a table of `cap` slots, at most
 uint32_t qpp_internal_plan_max_items(uint32_t n, uint32_t cap);
 int qpp_internal_plan_nokey(const qpp_plan *p, qpp_result *d_res, hipStream_t s);
+
+// A session's buffers for a caller in another translation unit
+// (qpp_session_route_unprotect): the staging reserved for `bytes` of input and
+// of output and `packets` packets, as qpp_session_stage does, and `scratch`
+// bytes of pinned (h_scratch) and device (d_scratch) memory of the session
+// that no other call uses.  Valid until the next call on the session.
+struct qpp_session_bufs {
+    hipStream_t stream;
+    uint8_t *h_in, *h_out, *d_in, *d_out;
+    uint8_t *h_scratch, *d_scratch;
+};
+int qpp_internal_session_bufs(qpp_session *s, size_t bytes, uint32_t packets, size_t scratch,
+                              qpp_session_bufs *out);

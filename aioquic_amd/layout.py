@@ -70,8 +70,23 @@ INITIAL = np.dtype(
 )
 SLOT_NONE = 0xFFFFFFFF  # QPP_SLOT_NONE: derive this direction but do not install it
 CID_MAX = 20
+# qpp_cid_entry: one connection ID of a CidMap and the caller's connection index
+CID_ENTRY = np.dtype(
+    [
+        ("conn", "<u4"),
+        ("cid_len", "u1"),
+        ("rsv", "u1", (3,)),
+        ("cid", "u1", (20,)),
+        ("rsv2", "<u4"),
+    ]
+)
+# qpp_route_rec: where a received datagram belongs (conn, or CONN_NONE) and its R_* class
+ROUTE = np.dtype([("conn", "<u4"), ("cls", "u1"), ("rsv", "u1", (3,))])
+CONN_NONE = 0xFFFFFFFF
+R_SHORT, R_LONG, R_UNKNOWN_CID, R_MALFORMED, R_BAD_CONN = 0, 1, 2, 3, 4
 assert DESC.itemsize == 40 and RESULT.itemsize == 16 and KEY_MATERIAL.itemsize == 84
 assert SECRET.itemsize == 80 and INITIAL.itemsize == 32
+assert CID_ENTRY.itemsize == 32 and ROUTE.itemsize == 8
 
 
 def key_material(slot: int, suite: int, key: bytes, iv: bytes, hp: bytes, key_phase: int = 0):
@@ -111,5 +126,17 @@ def initial_record(slot_client: int, slot_server: int, cid: bytes, *, v2: bool =
     rec["slot_server"] = slot_server
     rec["cid_len"] = len(cid)
     rec["flags"] = DERIVE_V2 if v2 else 0
+    rec["cid"][0, : len(cid)] = np.frombuffer(cid, dtype=np.uint8)
+    return rec
+
+
+def cid_entry(cid: bytes, conn: int = 0):
+    """One qpp_cid_entry: a connection ID (1..20 bytes) and the connection
+    index it routes to (ignored by CidMap.remove)."""
+    if not 1 <= len(cid) <= CID_MAX:
+        raise ValueError("connection ID must be 1..20 bytes")
+    rec = np.zeros(1, dtype=CID_ENTRY)
+    rec["conn"] = conn
+    rec["cid_len"] = len(cid)
     rec["cid"][0, : len(cid)] = np.frombuffer(cid, dtype=np.uint8)
     return rec

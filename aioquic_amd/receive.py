@@ -17,6 +17,11 @@ vectorised path: encrypted offset = 1 + host CID length, one packet per
 datagram (a short-header packet always runs to the end of its datagram,
 RFC 9000 sec. 12.2), no per-packet header parse.
 
+receive_routed takes raw datagrams nobody has demultiplexed: the device
+routes each to its connection by connection ID (route.CidRouter, qpp_route)
+in the same call that unprotects it, in place of the server's per-datagram
+routing (asyncio/server.py:60-152).
+
 The connection-level checks around the decrypt follow the reference too:
 a connection that lists its host CIDs drops packets for other CIDs (clients:
 every packet, servers: Handshake packets, "unknown_connection_id",
@@ -35,6 +40,7 @@ from typing import Any, Dict, List, NamedTuple, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _crypto
+from . import layout as L
 from ._crypto import CryptoError
 from .batch_io import ConnectionClosedError, ReceiveBatch, ReservedBitsError, default_slots
 from .buffer import Buffer
@@ -334,3 +340,93 @@ def _apply_closes(items, out: list) -> list:
                     break
         k = e
     return new
+
+
+def receive_routed(router, datagrams: Sequence[bytes]) -> Tuple[List[ReceivedPacket], List[Tuple[int, int]]]:
+    """receive_datagrams for raw datagrams nobody has demultiplexed: the
+    device routes each to its connection by connection ID (route.CidRouter,
+    qpp_route), instead of the reference's per-datagram pull_quic_header and
+    dict lookup (asyncio/server.py:60-152).
+
+    Returns (records, unrouted).  `records` are the ReceivedPackets of the
+    routed datagrams in order -- what receive_datagrams returns for
+    [(router.conns[c], datagram), ...] over them, with the same sequential
+    semantics -- and .datagram indexes the caller's list.  `unrouted` is
+    [(index, layout.R_* class)] of everything with no connection: an unknown
+    CID, a long header with an unknown DCID, a malformed datagram -- the
+    caller's new-connection, stateless-reset and drop business (:86-152).
+
+    When every routed datagram is a short header, the batch is staged once and
+    one call routes and unprotects it (_crypto.receive_routed).  A long header
+    to a known connection (Handshake traffic to a host CID), or a client that
+    checks its host CIDs, sends the routed datagrams through receive_datagrams
+    instead; their bytes are then uploaded twice, once to route and once to
+    unprotect."""
+    datagrams = datagrams if isinstance(datagrams, list) else list(datagrams)
+    if not datagrams:
+        return [], []
+    conns = router.conns
+    general = any(c is not None and c.is_client and c.host_cids is not None for c in conns)
+    pix: dict = {}
+    six: dict = {}
+    upairs, uspaces, c_pair, c_space = [], [], [], []
+    for conn in conns:
+        if conn is None:
+            c_pair.append(-1)
+            c_space.append(-1)
+            continue
+        pair, space = conn.pair_and_space(Epoch.ONE_RTT, None)
+        if id(pair) not in pix:
+            pix[id(pair)] = len(upairs)
+            upairs.append(pair)
+        if id(space) not in six:
+            six[id(space)] = len(uspaces)
+            uspaces.append(space)
+        c_pair.append(pix[id(pair)])
+        c_space.append(six[id(space)])
+    slots = default_slots()
+    keyed = [k for k, p in enumerate(upairs) if p.recv.aead is not None]
+    # one more pair (no key) and space than there are: a retired index points at them
+    pslot = np.full(len(upairs) + 1, 0xFFFFFFFF, np.uint32)
+    if keyed:
+        rc = [upairs[k].recv for k in keyed]
+        pslot[keyed] = slots.assign([(c.aead, c.hp, c.key_phase) for c in rc])
+    sexp = np.asarray([sp.expected_packet_number & 0xFFFFFFFFFFFFFFFF for sp in uspaces] + [0], np.uint64)
+    a_pair = np.asarray(c_pair, np.int64)
+    a_space = np.asarray(c_space, np.int64)
+    a_pair[a_pair < 0] = len(upairs)
+    a_space[a_space < 0] = len(uspaces)
+    route_b, walked = _crypto.receive_routed(
+        slots.table, router.map, router.host_cid_length, datagrams, a_pair.astype(np.uint32).tobytes(),
+        a_space.astype(np.uint32).tobytes(), pslot.tobytes(), sexp.tobytes(), ReceivedPacket, QuicPacketType.ONE_RTT,
+        Epoch.ONE_RTT, bytes(bool(c is not None and c.closed) for c in conns), 0 if general else 1)
+    route = np.frombuffer(route_b, dtype=L.ROUTE)
+    cls, rconn = route["cls"], route["conn"]
+    routed = ((cls == L.R_SHORT) | (cls == L.R_LONG)) & (rconn != L.CONN_NONE)
+    unrouted = [(int(i), int(cls[i])) for i in np.flatnonzero(~routed)]
+    idx = np.flatnonzero(routed)
+    if walked is None:
+        items = [(conns[rconn[i]], datagrams[i]) for i in idx.tolist()]
+        back = idx.tolist()
+        return [r._replace(datagram=back[r.datagram]) for r in receive_datagrams(items)], unrouted
+    recs, deferred, sexp2, closed = walked
+    new = np.frombuffer(sexp2, dtype=np.uint64)
+    for k in np.flatnonzero(new != sexp).tolist():
+        uspaces[k].expected_packet_number = int(new[k])
+    for k, f in enumerate(closed):
+        if f and conns[k] is not None:
+            conns[k].closed = True
+    if deferred:
+        # key-phase flips and numbers decoded under a stale expected number:
+        # the general walk takes them in order from the state left above
+        rb = ReceiveBatch(slots=slots)
+        at = idx.tolist()
+        for j in deferred:
+            conn = conns[rconn[at[j]]]
+            pair, space = conn.pair_and_space(Epoch.ONE_RTT, None)
+            rb.add(pair, datagrams[at[j]], 1 + conn.host_cid_length, space=space, conn=conn, reserved_mask=_RSV_SHORT)
+        for j, res in zip(deferred, rb.run()):
+            recs[j] = _record((at[j], 0, None, QuicPacketType.ONE_RTT, Epoch.ONE_RTT), res)
+            if isinstance(res, ReservedBitsError):
+                conns[rconn[at[j]]].closed = True
+    return recs, unrouted

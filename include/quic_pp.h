@@ -272,6 +272,102 @@ int qpp_unprotect_planned(const qpp_keytab *kt, const qpp_plan *p, const qpp_des
                           uint32_t n, const uint8_t *d_in, uint8_t *d_out, qpp_result *d_res,
                           void *stream);
 
+/* Routing received datagrams to connections by connection ID, on the device.
+ * Replaces the per-datagram routing of the reference's server
+ * (src/aioquic/asyncio/server.py:60-152: pull_quic_header,
+ * quic/packet.py:181-267, in Python, then
+ * self._protocols.get(header.destination_cid)) and its CID bookkeeping
+ * (server.py:154-170: _connection_id_issued / _connection_id_retired).
+ *
+ * A qpp_cidmap maps connection IDs of 1..QPP_CID_MAX bytes to the caller's
+ * connection indices.  It is an open-addressing table of 32-byte buckets
+ * (conn, cid_len, cid[20] zero-padded) with linear probing from
+ * hash(cid_len, cid) & (buckets - 1), buckets = the power of two >= 2 x
+ * capacity, at least 16.  The host keeps the authoritative mirror and alone
+ * decides where an entry lives; put and remove change the mirror and then
+ * scatter only the buckets they changed to the device copy (never the whole
+ * table).  The device only reads the table, in qpp_route: no device-side
+ * inserts, no atomics, no races.  A lookup stops at an empty bucket and is
+ * bounded by `buckets` probes whatever the table holds.
+ *
+ * put = _connection_id_issued, remove = _connection_id_retired; a batched put
+ * serves a burst of new connections.  Both are synchronous, like
+ * qpp_keytab_derive: on return the device table is current for every later
+ * launch (a launch still in flight on another stream is the caller's race).
+ * Put of a CID already present replaces its conn; the last duplicate inside
+ * one call wins.  Removing an absent CID is ignored; remove ignores conn.
+ * Removal is by backward shift (no tombstones, never a rebuild): the entries
+ * of the cluster behind the removed one move up, so after any sequence of
+ * puts and removes every remaining CID is found.  One removal rewrites the
+ * buckets of its own cluster only, an expected 1.5 at the table's maximum load
+ * of 1/2, so a full table's worth of churn (capacity removes and capacity
+ * puts) costs about 2.5 x capacity bucket writes on the host and as many
+ * 32-byte stores on the device, spread over the calls that made them.
+ * QPP_E_ARG with nothing changed, checked before the first change: NULL
+ * arguments with n > 0, a cid_len of 0 or > QPP_CID_MAX, a put that would take
+ * count past capacity (capacity itself: 1..2^22).  n == 0 returns QPP_OK.
+ * A map is single-threaded for put / remove; launches only read it. */
+#define QPP_CONN_NONE 0xffffffffu
+typedef struct qpp_cid_entry {
+    uint32_t conn;       /* caller's connection index */
+    uint8_t cid_len;     /* 1..QPP_CID_MAX */
+    uint8_t rsv[3];
+    uint8_t cid[20];     /* bytes past cid_len are ignored */
+    uint32_t rsv2;
+} qpp_cid_entry;         /* 32 bytes */
+typedef struct qpp_cidmap qpp_cidmap;
+int qpp_cidmap_create(uint32_t capacity, qpp_cidmap **out);
+/* Every launch that uses the map must have completed before it is destroyed. */
+void qpp_cidmap_destroy(qpp_cidmap *m);
+uint32_t qpp_cidmap_count(const qpp_cidmap *m);
+int qpp_cidmap_put(qpp_cidmap *m, const qpp_cid_entry *e, uint32_t n, void *stream);
+int qpp_cidmap_remove(qpp_cidmap *m, const qpp_cid_entry *e, uint32_t n, void *stream);
+/* The host mirror's answer: the CID's conn, or QPP_CONN_NONE. */
+uint32_t qpp_cidmap_find(const qpp_cidmap *m, const uint8_t *cid, uint32_t cid_len);
+/* The CID's home bucket (diagnostic / test hook; QPP_CONN_NONE for a bad length). */
+uint32_t qpp_cidmap_home(const qpp_cidmap *m, const uint8_t *cid, uint32_t cid_len);
+uint32_t qpp_cidmap_buckets(const qpp_cidmap *m);
+
+/* qpp_route: n raw datagrams (d_len[i] bytes at d_in + d_off[i], no alignment)
+ * to qpp_unprotect-ready descriptors, one lane per datagram (asynchronous on
+ * `stream`).  cid_len is the server's fixed host CID length
+ * (configuration.connection_id_length), 1..QPP_CID_MAX, else QPP_E_ARG.  A lane
+ * reads bytes [0, 1 + cid_len) of a short-header datagram and
+ * [0, 6 + DCID length) of a long-header one, never a byte past its d_len[i].
+ * Everything that changes per batch lives in two caller-owned device arrays
+ * indexed by conn: d_conn_slot (the receive key slot or QPP_SLOT_NONE) and
+ * d_conn_expected (the packet number space's expected packet number); the map
+ * changes only when CIDs are issued or retired.
+ *
+ * d_route[i] = (conn, cls).  For QPP_R_SHORT, d_desc[i] = {in_off = out_off =
+ * d_off[i], len = d_len[i], hdr_len = 1 + cid_len, flags = desc_flags, pn =
+ * d_conn_expected[conn], slot = d_conn_slot[conn], rsv = 0}; a short packet
+ * too short to unprotect is still routed and gets QPP_S_LENGTH from
+ * qpp_unprotect as ever.  For every other class d_desc[i] = {in_off = out_off
+ * = d_off[i], len = 0, hdr_len = 0, flags = desc_flags, pn = 0, slot =
+ * QPP_SLOT_NONE, rsv = 0}: qpp_unprotect reports QPP_S_NO_KEY for it and
+ * touches nothing, and its offsets keep its item's 32-bit views where its
+ * neighbours are (Buffers, above).  d_desc may be NULL: only d_route is
+ * written.  The descriptors feed qpp_plan_build + qpp_unprotect_planned, or
+ * qpp_unprotect, unchanged. */
+#define QPP_R_SHORT 0        /* short header, CID known: the descriptor is ready for qpp_unprotect */
+#define QPP_R_LONG 1         /* long header (bit 7): conn = its DCID's connection or QPP_CONN_NONE;
+                                the packets of the datagram are the host walk's */
+#define QPP_R_UNKNOWN_CID 2  /* short header, CID not in the map */
+#define QPP_R_MALFORMED 3    /* empty; (b0 & 0xC0) == 0; short and len < 1 + cid_len; long and
+                                len < 6, DCID length > 20 or len < 6 + DCID length */
+#define QPP_R_BAD_CONN 4     /* the entry's conn >= n_conn (either header form): nothing of the
+                                conn arrays was read; conn is the entry's */
+typedef struct qpp_route_rec {
+    uint32_t conn;           /* connection index, or QPP_CONN_NONE */
+    uint8_t cls;             /* QPP_R_* */
+    uint8_t rsv[3];
+} qpp_route_rec;             /* 8 bytes */
+int qpp_route(const qpp_cidmap *m, uint32_t cid_len, const uint64_t *d_off, const uint32_t *d_len,
+              uint32_t n, const uint8_t *d_in, const uint32_t *d_conn_slot,
+              const uint64_t *d_conn_expected, uint32_t n_conn, uint16_t desc_flags,
+              qpp_desc *d_desc /* may be NULL */, qpp_route_rec *d_route, void *stream);
+
 /* Header-protection masks: replaces HeaderProtection_mask (_crypto.c:278-287).
  * d_samples: n x 16 bytes, d_masks: n x 16 bytes (first 5 used). */
 int qpp_hp_mask(const qpp_keytab *kt, const uint32_t *d_slots, const uint8_t *d_samples,
@@ -293,6 +389,20 @@ int qpp_session_unprotect(qpp_session *s, const qpp_keytab *kt, const qpp_desc *
                           size_t out_len, qpp_result *res);
 int qpp_session_hp_mask(qpp_session *s, const qpp_keytab *kt, const uint32_t *slots,
                         const uint8_t *samples, uint32_t n, uint8_t *masks);
+/* qpp_route + qpp_unprotect on host buffers: one H2D of the datagram bytes
+ * and the small arrays, the routing kernel, the unplanned unprotect over all
+ * n descriptors, one D2H of output, descriptors (desc_out may be NULL), route
+ * records and results.  Serial form only: there is no chunked pipeline for
+ * this call, whatever the batch's size.  Works with the session's own pinned
+ * staging (qpp_session_stage) as `in` / `out`, like the calls above.  The
+ * host checks every off[i] + len[i] <= in_len and <= out_len before anything
+ * is launched: a violation is QPP_E_ARG (the caller's own arrays are wrong)
+ * and nothing is touched.  Output bytes no packet writes are zeros. */
+int qpp_session_route_unprotect(qpp_session *s, const qpp_keytab *kt, const qpp_cidmap *m, uint32_t cid_len,
+                                const uint64_t *off, const uint32_t *len, uint32_t n, const uint8_t *in,
+                                size_t in_len, const uint32_t *conn_slot, const uint64_t *conn_expected,
+                                uint32_t n_conn, uint16_t desc_flags, uint8_t *out, size_t out_len,
+                                qpp_desc *desc_out, qpp_route_rec *route_out, qpp_result *res);
 /* The session's own pinned staging buffers, sized for at least `bytes` of
  * input and of output and n packets; valid until the next call on the
  * session.  A caller that assembles its input straight into *h_in and passes

@@ -1,0 +1,243 @@
+#!/usr/bin/env python3
+"""Routing received datagrams by connection ID on the device (qpp_route), timed
+on a GPU box.  One process, one GPU.  Prints one JSON object (and writes it to
+--out).
+
+The traffic is n datagrams of 1200 B (short header | 8-byte CID | 2-byte packet
+number, the bench workload's packet) over C connections (default 4096, three
+suites) in random arrival order, for n = 1 Mi and 64 Ki.
+
+  device   on device buffers, timed with events on the stream, per n:
+             k_route                  raw datagrams -> descriptors + route records
+             bucket + unprotect       qpp_plan_build + qpp_unprotect_planned of
+                                      those descriptors (the launch k_route feeds)
+             unprotect alone          the planned launch without the plan build
+  host     from a list of bytes, wall time, per n of --host-sizes:
+             receive_routed           one call: stage, route + unprotect, walk
+             dict + receive_datagrams a Python routing pass (data[1:9] dict
+                                      lookup per datagram, the reference's
+                                      asyncio/server.py:60-152 without its header
+                                      parse) and receive_datagrams of the items
+
+The ways alternate in one process after --warmup rounds; median, min and max
+of --runs rounds.  Every round starts from the same connection state (expected
+packet numbers reset outside the timings).  The two host ways' records are
+compared at the end: a mismatch fails the run.
+"""
+
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import signal
+import statistics
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def _stats(xs):
+    return {"median_ms": round(statistics.median(xs), 4), "min_ms": round(min(xs), 4),
+            "max_ms": round(max(xs), 4)}
+
+
+class Space:
+    expected_packet_number = 0
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--conns", type=int, default=4096)
+    ap.add_argument("--sizes", default="1048576,65536", help="datagrams per batch, device part")
+    ap.add_argument("--host-sizes", default="1048576,65536", help="datagrams per batch, host part ('' = skip)")
+    ap.add_argument("--runs", type=int, default=11)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--timeout", type=int, default=900, help="seconds before the run gives up")
+    ap.add_argument("--out", default=None, help="also write the JSON object to this file")
+    a = ap.parse_args()
+    if a.runs < 10:
+        ap.error("--runs must be at least 10")
+    signal.signal(signal.SIGALRM, lambda *_: sys.exit("bench_route: timed out"))
+    signal.alarm(a.timeout)
+
+    import torch
+
+    from aioquic_amd import layout as L
+    from aioquic_amd import receive as R
+    from aioquic_amd.batch import PacketEngine
+    from aioquic_amd.bench_data import HDR_LEN, SLOT_BYTES, make_workload
+    from aioquic_amd.crypto import CryptoPair, derive_key_iv_hp
+    from aioquic_amd.packet import QuicProtocolVersion
+    from aioquic_amd.route import CidRouter
+    from aioquic_amd.tls import CipherSuite, Epoch
+
+    torch.cuda.set_device(0)
+    dev = torch.device("cuda", 0)
+    C = a.conns
+    rng = np.random.default_rng(0xC1D)
+    suites = [(L.AES_128_GCM, CipherSuite.AES_128_GCM_SHA256, 32), (L.AES_256_GCM, CipherSuite.AES_256_GCM_SHA384, 48),
+              (L.CHACHA20_POLY1305, CipherSuite.CHACHA20_POLY1305_SHA256, 32)]
+    version = int(QuicProtocolVersion.VERSION_1)
+    cid = rng.integers(0, 256, (C, 8), dtype=np.uint8)
+    cid[:, :4] = np.arange(C, dtype=">u4").view(np.uint8).reshape(C, 4)  # distinct
+    cids = [cid[c].tobytes() for c in range(C)]
+    keys = np.zeros(C, dtype=L.KEY_MATERIAL)
+    secrets = []
+    for c in range(C):
+        suite, cs, slen = suites[c % 3]
+        secret = rng.bytes(slen)
+        secrets.append((cs, secret))
+        key, iv, hp = derive_key_iv_hp(cipher_suite=cs, secret=secret, version=version)
+        keys[c] = L.key_material(c, suite, key, iv, hp)[0]
+    eng = PacketEngine(C)
+    eng.set_key_records(keys)
+    cmap = eng.cid_map(C)
+    cmap.put(np.concatenate([L.cid_entry(x, c) for c, x in enumerate(cids)]).tobytes())
+
+    def traffic(n):
+        """(wire bytes on the device, connection per datagram): the bench
+        workload's packets, each with its connection's CID, protected here."""
+        w = make_workload(n, n_keys=C, seed=0x70 + n % 251, order="random")
+        conn = w.desc["slot"].astype(np.int64)
+        view = w.plain[: n * SLOT_BYTES].reshape(n, SLOT_BYTES)
+        view[:, 1:9] = cid[conn]
+        d_plain = torch.from_numpy(w.plain).to(dev)
+        d_wire = torch.zeros(w.wire_size, dtype=torch.uint8, device=dev)
+        d_res = torch.zeros(n * 16, dtype=torch.uint8, device=dev)
+        d_desc = torch.from_numpy(w.desc.view(np.uint8)).to(dev)
+        eng.protect(d_desc, n, d_plain, d_wire, d_res, plan=eng.bucket(d_desc, n))
+        torch.cuda.synchronize()
+        assert (d_res.cpu().numpy().view(L.RESULT)["status"] == 0).all()
+        return d_wire, conn, w
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    out = {"tool": "bench_route", "connections": C, "datagram_bytes": SLOT_BYTES, "runs": a.runs,
+           "warmup": a.warmup, "map_buckets": cmap.buckets, "device": {}, "host": {}}
+    host_sizes = [int(x) for x in a.host_sizes.split(",") if x]
+    wires = {}
+    for n in [int(x) for x in a.sizes.split(",") if x]:
+        d_wire, conn, w = traffic(n)
+        if n in host_sizes:
+            wires[n] = (d_wire.cpu().numpy(), conn)
+        t = lambda x: torch.from_numpy(np.ascontiguousarray(x).view(np.uint8).reshape(-1)).to(dev)
+        d_off = t(np.arange(n, dtype=np.uint64) * SLOT_BYTES)
+        d_len = t(np.full(n, SLOT_BYTES, np.uint32))
+        d_slot = t(np.arange(C, dtype=np.uint32))
+        d_exp = t(np.zeros(C, np.uint64))
+        d_desc = torch.zeros(n * 40, dtype=torch.uint8, device=dev)
+        d_route = torch.zeros(n * 8, dtype=torch.uint8, device=dev)
+        d_out = torch.zeros(w.wire_size, dtype=torch.uint8, device=dev)
+        d_res = torch.zeros(n * 16, dtype=torch.uint8, device=dev)
+        route = lambda: eng.route(cmap, 8, d_off, d_len, n, d_wire, d_slot, d_exp, C, d_route, desc=d_desc)
+        both = lambda: eng.unprotect(d_desc, n, d_wire, d_out, d_res, plan=eng.bucket(d_desc, n))
+        plan = [None]
+        alone = lambda: eng.unprotect(d_desc, n, d_wire, d_out, d_res, plan=plan[0])
+        t_route, t_both, t_alone = [], [], []
+        for r in range(a.warmup + a.runs):
+            x = timed(route)
+            y = timed(both)
+            plan[0] = eng.bucket(d_desc, n)
+            z = timed(alone)
+            if r >= a.warmup:
+                t_route.append(x), t_both.append(y), t_alone.append(z)
+        torch.cuda.synchronize()
+        rr = d_route.cpu().numpy().view(L.ROUTE)
+        res = d_res.cpu().numpy().view(L.RESULT)
+        ok = bool((rr["cls"] == L.R_SHORT).all() and (rr["conn"] == conn).all() and (res["status"] == 0).all()
+                  and np.array_equal(d_out.cpu().numpy().reshape(-1)[: n * SLOT_BYTES].reshape(n, SLOT_BYTES)[:, :HDR_LEN],
+                                     w.plain[: n * SLOT_BYTES].reshape(n, SLOT_BYTES)[:, :HDR_LEN]))
+        mr, mb = statistics.median(t_route), statistics.median(t_both)
+        out["device"][str(n)] = {
+            "k_route": _stats(t_route), "bucket_plus_unprotect_planned": _stats(t_both),
+            "unprotect_planned_alone": _stats(t_alone),
+            "k_route_over_planned_unprotect": round(mr / mb, 4),
+            "k_route_ns_per_datagram": round(mr * 1e6 / n, 3),
+            "k_route_gb_per_s_at_200B": round(200 * n / (mr * 1e-3) / 1e9, 1),
+            "routed_and_unprotected_ok": ok,
+        }
+        if not ok:
+            print(json.dumps(out))
+            sys.exit("bench_route: the routed batch did not unprotect")
+        del d_wire, d_out, d_desc, d_route, d_res, w
+        torch.cuda.empty_cache()
+
+    # ---- host part: list of bytes in, records out
+    conns = []
+    for c in range(C if host_sizes else 0):
+        cs, secret = secrets[c]
+        pair = CryptoPair()
+        pair.recv.setup(cipher_suite=cs, secret=secret, version=version)
+        conns.append(R.ConnectionKeys(cryptos={Epoch.ONE_RTT: pair}, spaces={Epoch.ONE_RTT: Space()},
+                                      host_cid_length=8))
+    router = CidRouter(8, C) if host_sizes else None
+    for c, conn in enumerate(conns):
+        router.add(cids[c], conn)
+    by_cid = {cids[c]: conn for c, conn in enumerate(conns)}
+
+    def reset():
+        for conn in conns:
+            conn.spaces[Epoch.ONE_RTT].expected_packet_number = 0
+
+    same = True
+    for n in host_sizes:
+        if n not in wires:
+            d_wire, conn, _ = traffic(n)
+            wires[n] = (d_wire.cpu().numpy(), conn)
+        wire, conn = wires.pop(n)
+        raw = wire[: n * SLOT_BYTES].tobytes()
+        datagrams = [raw[i * SLOT_BYTES:(i + 1) * SLOT_BYTES] for i in range(n)]
+        del raw, wire
+        t_routed, t_dict, t_pass = [], [], []
+        got = want = None
+        for r in range(a.warmup + a.runs):
+            reset()
+            t0 = time.perf_counter()
+            got, unrouted = R.receive_routed(router, datagrams)
+            t1 = time.perf_counter()
+            reset()
+            t2 = time.perf_counter()
+            items = [(by_cid[d[1:9]], d) for d in datagrams]
+            t3 = time.perf_counter()
+            want = R.receive_datagrams(items)
+            t4 = time.perf_counter()
+            if r >= a.warmup:
+                t_routed.append((t1 - t0) * 1e3)
+                t_pass.append((t3 - t2) * 1e3)
+                t_dict.append((t4 - t2) * 1e3)
+            if r + 1 < a.warmup + a.runs:
+                del got, want, items
+        eq = not unrouted and len(got) == len(want) == n and all(
+            g == w_ and g.dropped is None for g, w_ in zip(got, want))
+        same = same and eq
+        mr, md = statistics.median(t_routed), statistics.median(t_dict)
+        out["host"][str(n)] = {
+            "receive_routed": dict(_stats(t_routed), datagrams_per_s=round(n / (mr * 1e-3))),
+            "dict_pass_plus_receive_datagrams": dict(_stats(t_dict), dict_pass=_stats(t_pass),
+                                                     datagrams_per_s=round(n / (md * 1e-3))),
+            "dict_way_over_routed": round(md / mr, 3),
+            "same_records": bool(eq),
+        }
+        del datagrams, got, want
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    if not same:
+        sys.exit("bench_route: the two host ways' records differ")
+
+
+if __name__ == "__main__":
+    main()
