@@ -61,19 +61,10 @@ constexpr int kChRegion = 64 * 16 + 16;
 constexpr int kChStage = 4 * kChRegion;
 
 // pw entries: 1, r, r^2 .. r^5, r^8, r^13 .. r^16
-#ifndef QPP_CH_POLY4
-#define QPP_CH_POLY4 1  // study switch: 0 = one Horner multiply (and carry) per Poly1305 block
-#endif
-#ifndef QPP_CH_DPP_T
-#define QPP_CH_DPP_T 0  // study switch: one-round launches transpose a step's output blocks by DPP
-#endif
-#ifndef QPP_CH_DIRECT_ST
-#define QPP_CH_DIRECT_ST 0  // study switch: 1 = each lane stores its own blocks (no LDS round trip back)
-#endif
-#ifndef QPP_CH_CARRY_AT
-#define QPP_CH_CARRY_AT 7  // study switch: the double round after which the chunk sum is carried
-#endif
-constexpr int kPwOne = 0, kPw1 = 1, kPw8 = 6, kPw13 = 7, kPwEntries = QPP_CH_POLY4 ? 11 : 7;
+constexpr int kPwOne = 0, kPw1 = 1, kPw8 = 6, kPw13 = 7, kPwEntries = 11;
+// the double round of the next ChaCha20 block after which a chunk's Poly1305
+// sum is carried (its four products follow double rounds 1, 3, 5, 7)
+constexpr int kChCarryAt = 7;
 
 template <int WG>
 struct __attribute__((aligned(16))) ChachaSmem {
@@ -640,7 +631,7 @@ template <int NR, bool ENC, int BPL, int SUITE, bool PRIO, bool CLDS = false>
 __device__ __forceinline__ u32x4 gcm_packet(const Pkt &P, const KeySlot *ks, const u32x4 h0,
                                             const uint32_t *rk, int sub, const GhashTabs &G,
                                             const uint8_t *te, const Bufs &B, uint32_t ioff, uint32_t ooff,
-                                            u32x4 &got_tag, uint32_t pbase = 0u)
+                                            u32x4 &got_tag)
 {
     const LdsTe T{te, (lane_fresh() & 31) * 4};
     const int hlen = P.hlen, clen = P.clen;
@@ -836,20 +827,10 @@ __device__ __forceinline__ u32x4 gcm_packet(const Pkt &P, const KeySlot *ks, con
                     // persistent 1024-thread workgroups, for every item or
                     // only each share's last ones, no gain at 1 Mi)
                     const int kr = __builtin_amdgcn_readfirstlane(k);
-#if QPP_COMBO_PRIO
-                    // study: the workgroup's share level (pbase 0 or 2) plus
-                    // one for the item's first half
-                    const uint32_t lv = __builtin_amdgcn_readfirstlane(pbase) + (kr >= 5 ? 1u : 0u);
-                    if (lv >= 3) __builtin_amdgcn_s_setprio(3);
-                    else if (lv == 2) __builtin_amdgcn_s_setprio(2);
-                    else if (lv == 1) __builtin_amdgcn_s_setprio(1);
-                    else __builtin_amdgcn_s_setprio(0);
-#else
                     if (kr >= 7) __builtin_amdgcn_s_setprio(3);
                     else if (kr >= 4) __builtin_amdgcn_s_setprio(2);
                     else if (kr >= 2) __builtin_amdgcn_s_setprio(1);
                     else __builtin_amdgcn_s_setprio(0);
-#endif
                 }
                 one2(k, std::false_type{});
             }
@@ -1034,26 +1015,6 @@ __device__ void chacha_packet(Pkt &P, const KeySlot *ks, int sub, uint8_t *scr, 
     // the block's independent quarter rounds.  Blocks that do not exist
     // (c < 0: the key unit; past the payload's end) multiply by one and add
     // zero, which leaves the chain as it is.
-#if !QPP_CH_POLY4
-    auto poly_blk = [&](const u32x4 (&x)[4], int c, int b) {
-        {
-            const int i = 4 * c + b;
-            const bool valid = c >= 0 && i < n_c;
-            const P130 m = p130_block(x[b]);
-            const P130 &rm = (b == 3 && c + 4 < chunks) ? r13 : r;
-            // (x[b] is zero for a block that does not exist: only the 2^128
-            // bit of p130_block needs masking)
-            P130 a = acc, f;
-#pragma unroll
-            for (int l = 0; l < 5; ++l) {
-                a.v[l] += l < 4 ? m.v[l] : valid ? m.v[l] : 0u;
-                f.v[l] = valid ? rm.v[l] : (l == 0 ? 1u : 0u);
-            }
-            acc = p130_mul(a, f);
-        }
-    };
-#endif
-#if QPP_CH_POLY4
     // The chunk as one sum: the lane's chain moves by
     //   acc <- (acc + x0) r^e0 + x1 r^e1 + x2 r^e2 + x3 r^e3,
     // e = 16 .. 13 when the lane has a later chunk (its Horner steps r, r, r
@@ -1090,28 +1051,16 @@ __device__ void chacha_packet(Pkt &P, const KeySlot *ks, int sub, uint8_t *scr, 
         for (int b = 0; b < 4; ++b) poly_part(x, c, b);
         poly_carry();
     };
-#else
-    auto poly = [&](const u32x4 (&x)[4], int c) {
-#pragma unroll
-        for (int b = 0; b < 4; ++b) poly_blk(x, c, b);
-    };
-#endif
     // the memory side of step k: the lane's chunk c from region `sub` xor
     // its keystream, back through LDS to 4 coalesced stores, the next step's
     // LDS-DMA; x = the chunk's Poly1305 inputs
     auto chunk_io = [&](int k, int c, const uint32_t (&blk)[16], u32x4 (&x)[4]) {
         // (the DMA retires in issue order, after the previous step's stores:
         // vmcnt(0) waits for both)
-#ifdef QPP_CH_MEMPRIO
-        __builtin_amdgcn_s_setprio(QPP_CH_MEMPRIO);  // study: the memory side first
-#endif
         QPP_PROBE_AT(4);  // (probe build) the ChaCha20 block and Poly1305 before this wait
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         QPP_PROBE_AT(5);  // the wait for this step's input (and the last step's stores)
         uint8_t *mine = stage + sub * kChRegion + qoff;
-#if QPP_CH_DPP_T
-        u32x4 o4[4];
-#endif
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
             const int i = 4 * c + b;
@@ -1136,82 +1085,8 @@ __device__ void chacha_packet(Pkt &P, const KeySlot *ks, int sub, uint8_t *scr, 
                 }
             }
             if (valid && ENC && P.hp && i < 2) *(u32x4 *)(scr + 16 * i) = x[b];
-#if QPP_CH_DPP_T
-            if constexpr (PRIO) {
-                o4[b] = o;  // transposed across the quad below, no LDS round trip
-            } else {
-                *(u32x4 *)(mine + 16 * b) = o;
-            }
-#elif QPP_CH_DIRECT_ST
-            {
-                // the lane's own full block straight out (a quad's 4 stores
-                // of one instruction are 64 B apart; the 4 instructions
-                // complete the quad's 256 B)
-                const uint32_t so = (valid && nb >= 16 && !tiny) ? ooff + (uint32_t)(P.hlen + 16 * i) : kOob;
-                __builtin_amdgcn_raw_buffer_store_b128(o, B.out, (int)so, 0, 0);
-            }
-#else
             *(u32x4 *)(mine + 16 * b) = o;
-#endif
         }
-#if QPP_CH_DPP_T
-        if constexpr (PRIO) {
-            // one-round launches (latency-bound, VALU to spare): the quad's
-            // 4x4 transpose of blocks in registers, two DPP butterflies
-            // (lanes j^1, then j^2; each lane sends the block it replaces),
-            // so o4[t] = lane t's block `sub` = this lane's block of chunk
-            // 4k - 1 + t, for the same coalesced stores without writing the
-            // blocks back through LDS and reading them again
-            const bool p0 = (sub & 1) != 0, p1 = (sub & 2) != 0;
-#pragma unroll
-            for (int a = 0; a < 4; a += 2) {
-                const u32x4 snd = p0 ? o4[a] : o4[a + 1];
-                const u32x4 rcv = u32x4{quad_dpp<0xB1>(snd.x), quad_dpp<0xB1>(snd.y), quad_dpp<0xB1>(snd.z),
-                                        quad_dpp<0xB1>(snd.w)};
-                if (p0) o4[a] = rcv;
-                else o4[a + 1] = rcv;
-            }
-#pragma unroll
-            for (int a = 0; a < 2; ++a) {
-                const u32x4 snd = p1 ? o4[a] : o4[a + 2];
-                const u32x4 rcv = u32x4{quad_dpp<0x4E>(snd.x), quad_dpp<0x4E>(snd.y), quad_dpp<0x4E>(snd.z),
-                                        quad_dpp<0x4E>(snd.w)};
-                if (p1) o4[a] = rcv;
-                else o4[a + 2] = rcv;
-            }
-            // the xor consumed every lane's input: the regions are free
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_wave_barrier();
-            QPP_PROBE_AT(6);  // (probe build) xor and transpose
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const int i = 4 * (4 * k - 1 + t) + sub;
-                const uint32_t so = (i >= 0 && 16 * i + 16 <= P.clen && !tiny) ? ooff + (uint32_t)(P.hlen + 16 * i) : kOob;
-                __builtin_amdgcn_raw_buffer_store_b128(o4[t], B.out, (int)so, 0, 0);
-            }
-            QPP_PROBE_AT(8);  // (probe build) the stores' issue
-        } else {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_wave_barrier();
-            QPP_PROBE_AT(6);  // (probe build) xor through LDS
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const int i = 4 * (4 * k - 1 + t) + sub;
-                const uint32_t so = (i >= 0 && 16 * i + 16 <= P.clen && !tiny) ? ooff + (uint32_t)(P.hlen + 16 * i) : kOob;
-                const u32x4 v = *(const u32x4 *)(stage + t * kChRegion + qoff + 16 * sub);
-                __builtin_amdgcn_raw_buffer_store_b128(v, B.out, (int)so, 0, 0);
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_wave_barrier();
-            QPP_PROBE_AT(8);  // (probe build) the stores' reads and issue
-        }
-#elif QPP_CH_DIRECT_ST
-        // the xor consumed every lane's input: the regions are free for the
-        // next step's DMA
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_wave_barrier();
-        QPP_PROBE_AT(6);  // (probe build) xor and stores
-#else
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_wave_barrier();
         QPP_PROBE_AT(6);  // (probe build) xor through LDS
@@ -1229,11 +1104,7 @@ __device__ void chacha_packet(Pkt &P, const KeySlot *ks, int sub, uint8_t *scr, 
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_wave_barrier();
         QPP_PROBE_AT(8);  // (probe build) the stores' reads and issue
-#endif
         if (k + 1 < steps) dma(k + 1);
-#ifdef QPP_CH_MEMPRIO
-        __builtin_amdgcn_s_setprio(0);
-#endif
         QPP_PROBE_AT(3);  // (probe build) next step's DMA issue
     };
 
@@ -1257,7 +1128,6 @@ __device__ void chacha_packet(Pkt &P, const KeySlot *ks, int sub, uint8_t *scr, 
         const P130 b58 = p130_mul(r4, sub == 0 ? r : r4);
         const P130 r5 = p130_from_lane<0>(b58), r8 = p130_from_lane<1>(b58);
         r13 = p130_mul(r8, r5);
-#if QPP_CH_POLY4
         {
             // the chunk sums' powers r^13 .. r^16, one multiply per lane:
             // lane 0 r^13 r, lane 1 r^8 r^8, lane 2 r^13 r^2, lane 3 r^13
@@ -1269,7 +1139,6 @@ __device__ void chacha_packet(Pkt &P, const KeySlot *ks, int sub, uint8_t *scr, 
 #pragma unroll
             for (int l = 0; l < 5; ++l) pw[5 * slot + l] = pr.v[l];
         }
-#endif
         if (sub == 0) {  // the close's powers (kPwOne .. kPw8)
 #pragma unroll
             for (int l = 0; l < 5; ++l) {
@@ -1315,19 +1184,12 @@ __device__ void chacha_packet(Pkt &P, const KeySlot *ks, int sub, uint8_t *scr, 
         }
         const int c = 4 * k + sub - 1;
         uint32_t blk[16];
-        // the previous chunk's 4 Poly1305 blocks after double rounds 1, 3, 5, 7
-#if QPP_CH_POLY4
         // the previous chunk's 4 Poly1305 products after double rounds 1, 3,
         // 5, 7, its carry after the last
         chacha_block_beside(key, (uint32_t)(c + 1), n0, n1, n2, blk, [&](int i) {
             if (i & 1 && i < 8) poly_part(x, c - 4, i >> 1);
-            if (i == QPP_CH_CARRY_AT) poly_carry();
+            if (i == kChCarryAt) poly_carry();
         });
-#else
-        chacha_block_beside(key, (uint32_t)(c + 1), n0, n1, n2, blk, [&](int i) {
-            if (i & 1 && i < 8) poly_blk(x, c - 4, i >> 1);
-        });
-#endif
         // pin the chain here: otherwise the compiler sinks this Poly1305 step
         // to the next iteration's top (beside the loop's exit test), out of
         // the rounds' basic block
@@ -1604,20 +1466,6 @@ __device__ __forceinline__ void tab_release(SM &sm, uint32_t e)
     if (lane_fresh() == 0) atomicSub(&sm.eref[e], 1u);
 }
 
-// Study build only (-DQPP_STUDY_SYNTH, tools/build_variant.py): the north
-// star's descriptors and header byte 0 synthesized from the packet index
-// instead of loaded, to bound what prefetching them could gain (round 5,
-// VERDICT r4 item 3).  Wrong output by design: timing only.
-#ifdef QPP_STUDY_SYNTH
-__device__ __forceinline__ qpp_desc study_desc(const qpp_desc *, uint32_t p)
-{
-    return qpp_desc{1200ull * p, 1200ull * p, 1173u, 11, 0, (uint64_t)p, 0u, p};
-}
-#define QPP_DESC(i) study_desc(desc, (i))
-#else
-#define QPP_DESC(i) desc[i]
-#endif
-
 // Launch-wide item pool of a 1024-thread GCM launch (pool != null, a slot of
 // the key table's PoolRing): the workgroups' contiguous shares cover all but
 // the last 1/kPoolDiv of the launch's items, which any wave takes, once its
@@ -1630,22 +1478,7 @@ __device__ __forceinline__ qpp_desc study_desc(const qpp_desc *, uint32_t p)
 // over many keys the pooled items scatter each key over many workgroups'
 // GHASH table entries (config 4 -6 %, config 5 -0.4 %; the north star +0.4
 // to +1.6 %, profiles/r5ad_gcm_pool.txt).
-#ifndef QPP_POOL_DIV
-#define QPP_POOL_DIV 12  // build-time study switch
-#endif
-constexpr uint32_t kPoolDiv = QPP_POOL_DIV;
-#ifndef QPP_POOL512
-#define QPP_POOL512 0  // study switch: the item pool for the 512-thread shape too
-#endif
-#ifndef QPP_COMBO_PRIO
-#define QPP_COMBO_PRIO 0  // study switch: 512-thread shape, share level + item progress in one priority
-#endif
-#ifndef QPP_SHARE_PRIO
-#define QPP_SHARE_PRIO 0  // study switch: 512-thread shape, issue priority by the workgroup's share left
-#endif
-#ifndef QPP_PRIO512
-#define QPP_PRIO512 1  // study switch: issue priority by progress in the 512-thread shape
-#endif
+constexpr uint32_t kPoolDiv = 12;
 
 template <int SUITE, bool ENC, int WG, int BPL, bool CLDS = false>
 __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_gcm(const KeySlot *__restrict__ slots,
@@ -1718,23 +1551,6 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
             if (q >= pool_n) break;
             j = ib + stat + q;
         }
-#if QPP_COMBO_PRIO
-        uint32_t pbase = 0u;
-        if constexpr (WG == 512) pbase = (j < se && 2u * (se - j) > se - sb) ? 2u : 0u;
-#endif
-#if QPP_SHARE_PRIO
-        if constexpr (WG == 512) {
-            // the two workgroups of a CU progress through their shares
-            // together: the one with more of its share left issues first
-            // (pooled items, at the launch's end, at the bottom)
-            const uint32_t tot = se - sb, rem = j < se ? se - j : 0u;
-            const uint32_t pr = tot ? min(3u, (4u * rem) / (tot + 1u)) : 0u;
-            if (pr >= 3) __builtin_amdgcn_s_setprio(3);
-            else if (pr == 2) __builtin_amdgcn_s_setprio(2);
-            else if (pr == 1) __builtin_amdgcn_s_setprio(1);
-            else __builtin_amdgcn_s_setprio(0);
-        }
-#endif
         QPP_PROBE_AT(1);  // the previous item's tail, the grab
         QPP_PROBE_COUNT();
         // the item's positions [wb, we) of desc
@@ -1759,7 +1575,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
             const uint32_t t = tid_now(), p = pkt_of(t);
             uint64_t in0 = ~0ull, out0 = ~0ull;
             if (p < we) {
-                const qpp_desc d = QPP_DESC(p);
+                const qpp_desc d = desc[p];
                 in0 = d.in_off;
                 out0 = d.out_off;
                 if (d.slot >= cap && (t & 3) == 0) res[planned ? d.rsv : p] = qpp_result{d.pn, QPP_S_NO_KEY, 0, 0};
@@ -1772,13 +1588,9 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
         auto run_slot = [&](uint32_t cur) {
             const KeySlot *ks = slots + cur;
             const uint32_t t1 = tid_now(), p1 = pkt_of(t1);
-            const qpp_desc d = p1 < we ? QPP_DESC(p1) : qpp_desc{0, 0, 0, 0, 0, 0, kNoSlot, 0};
+            const qpp_desc d = p1 < we ? desc[p1] : qpp_desc{0, 0, 0, 0, 0, 0, kNoSlot, 0};
             if (slot_of(d, p1) != cur) return;  // the lambda's only early exit, at its top
-#ifdef QPP_STUDY_SYNTH
-            const HdrPre pre = {{0x41u, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, 0x41u};
-#else
             const HdrPre pre = prefetch_hdr<ENC>(d, gin, true);
-#endif
             const LdsTe T{sm.te, (t1 & 31) * 4};
             Pkt P = pkt_begin<ENC, SUITE>(d, pre, gin, gout, ks, T);
             if (P.status == QPP_S_OK) {
@@ -1798,16 +1610,12 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
                     const uint64_t pn = P.pn;
                     const int hlen = P.hlen;
                     u32x4 got_tag;
-                    const u32x4 tag = gcm_packet<kNR, ENC, BPL, SUITE, WG == 512 && QPP_PRIO512, CLDS>(P, ks, pre.h0, rk, t1 & 3, G, sm.te, B,
-                                                                       (uint32_t)ioff, (uint32_t)ooff, got_tag
-#if QPP_COMBO_PRIO
-                                                                       , pbase
-#endif
-                                                                       );
+                    const u32x4 tag = gcm_packet<kNR, ENC, BPL, SUITE, WG == 512, CLDS>(P, ks, pre.h0, rk, t1 & 3, G, sm.te, B,
+                                                                       (uint32_t)ioff, (uint32_t)ooff, got_tag);
                     QPP_PROBE_AT(6);
                     // everything below is re-derived after the step loop
                     const uint32_t t2 = tid_now(), p2 = pkt_of(t2);
-                    const qpp_desc d2 = QPP_DESC(p2);
+                    const qpp_desc d2 = desc[p2];
                     Pkt Q;
                     Q.src = gin + d2.in_off;
                     Q.dst = gout + d2.out_off;
@@ -1830,7 +1638,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
                 }
             }
             const uint32_t t3 = tid_now(), p3 = pkt_of(t3);
-            write_result<ENC>(res, planned ? QPP_DESC(p3).rsv : p3, t3 & 3, P);
+            write_result<ENC>(res, planned ? desc[p3].rsv : p3, t3 & 3, P);
             QPP_PROBE_AT(7);
         };
 
@@ -1841,7 +1649,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
 #pragma unroll 1
         for (int guard = 0; guard < 17; ++guard) {
             const uint32_t t = tid_now(), p = pkt_of(t);
-            const uint32_t s = p < we ? slot_of(QPP_DESC(p), p) : kNoSlot;
+            const uint32_t s = p < we ? slot_of(desc[p], p) : kNoSlot;
             const uint32_t cur = wave_min_u32((last == kNoSlot || s > last) ? s : kNoSlot);
             if (cur == kNoSlot) break;
             last = cur;
@@ -1880,7 +1688,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
             }
             if (fail) {
                 if (s == cur && (t & 3) == 0) {
-                    const qpp_desc d = QPP_DESC(p);
+                    const qpp_desc d = desc[p];
                     res[planned ? d.rsv : p] = qpp_result{d.pn, (uint16_t)fail, 0, 0};
                 }
                 continue;
@@ -1946,13 +1754,6 @@ __device__ __forceinline__ void chacha_wave(const WaveSpan &W, ChachaSmem<WG> &s
                                             const uint32_t *__restrict__ irange)
 {
     constexpr int SUITE = QPP_CHACHA20_POLY1305;
-#ifdef QPP_CH_STAGGER
-    {
-        // study: waves start QPP_CH_STAGGER x 64 cycles apart by their slot in the SIMD
-        const uint32_t slot = __builtin_amdgcn_s_getreg(4 | (0 << 6) | (3 << 11));
-        for (uint32_t i = 0; i < slot * QPP_CH_STAGGER; ++i) __builtin_amdgcn_s_sleep(1);
-    }
-#endif
     QPP_PROBE_AT(kProbeStart);
     if constexpr (PRIO) __builtin_amdgcn_s_setprio(3);  // set-up and key block: every wave at the top
     const uint32_t lim = W.e, planned = irange != nullptr;
@@ -2019,9 +1820,6 @@ __device__ __forceinline__ void chacha_wave(const WaveSpan &W, ChachaSmem<WG> &s
     QPP_PROBE_AT(9);
 }
 
-#ifndef QPP_CH_PERSIST
-#define QPP_CH_PERSIST 0  // study switch: > 0 = grid capped at that many rounds of resident workgroups, each looping
-#endif
 template <bool ENC, int WG, bool PRIO>
 __global__ __launch_bounds__(WG, kChachaWpe) void k_chacha(const KeySlot *__restrict__ slots,
                                                              uint32_t cap,
@@ -2035,20 +1833,9 @@ __global__ __launch_bounds__(WG, kChachaWpe) void k_chacha(const KeySlot *__rest
     constexpr int SUITE = QPP_CHACHA20_POLY1305;
     __shared__ ChachaSmem<WG> sm;
     const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-#if QPP_CH_PERSIST
-    // study: each wave walks the blocks blockIdx.x, + gridDim.x, ... on its
-    // own (no barrier: a wave that ends its item takes the next at once)
-#pragma unroll 1
-    for (uint32_t vb = blockIdx.x;; vb += gridDim.x) {
-        const WaveSpan W = wave_span<WG, SUITE>(n, items, irange, wv, vb);
-        if (W.empty_wg) break;
-        chacha_wave<ENC, WG, PRIO>(W, sm, slots, cap, desc, gin, gout, res, irange);
-    }
-#else
     const WaveSpan W = wave_span<WG, SUITE>(n, items, irange, wv, blockIdx.x);
     if (W.empty_wg) return;
     chacha_wave<ENC, WG, PRIO>(W, sm, slots, cap, desc, gin, gout, res, irange);
-#endif
 }
 
 // ----------------------------------------------------------- lone packets --
@@ -2808,8 +2595,8 @@ __global__ void k_clear_slots(KeySlot *slots, const uint32_t *idx, uint32_t n, u
     if (i < n && idx[i] < cap) slots[idx[i]].suite = 0xffu;
 }
 
-// PCIe copies by the GPU's own loads and stores (qpp_session's D2H legs, and
-// H2D under QPP_H2D_KERNEL): range y of the launch copies n_y bytes from src_y
+// PCIe copies by the GPU's own loads and stores (qpp_session's D2H legs):
+// range y of the launch copies n_y bytes from src_y
 // to dst_y, one of them a pinned host buffer's device view, in 16-byte
 // non-temporal accesses (D2H: posted PCIe writes; bytes at a range's unaligned
 // ends one by one).  The runtime's D2H
@@ -2894,16 +2681,6 @@ struct qpp_keytab {
     float trace_ms[2];
 };
 
-// QPP_GCM_POOL=0 (a study switch, read once per process): static shares only.
-static bool pool_choice()
-{
-    static const bool b = [] {
-        const char *v = getenv("QPP_GCM_POOL");
-        return !(v && v[0] == '0');
-    }();
-    return b;
-}
-
 // Launches that found every pool slot held and ran on static shares alone
 // (qpp_pool_fallbacks; tests/test_gpu_pool.py).
 static std::atomic<uint64_t> g_pool_fallbacks{0};
@@ -2915,7 +2692,7 @@ static std::atomic<uint64_t> g_close_lds_launches{0};
 static int pool_acquire(const qpp_keytab *kt)
 {
     PoolRing *r = kt->pool;
-    if (!r || !pool_choice()) return -1;
+    if (!r) return -1;
     std::lock_guard<std::mutex> l(r->mu);
     for (int i = 0; i < kPoolSlots; ++i) {
         const int sl = (r->next + i) % kPoolSlots;
@@ -3294,10 +3071,7 @@ int qpp_keytab_clear(qpp_keytab *kt, const uint32_t *slots, uint32_t n, void *st
 // persistent workgroup per CU, 4 waves per SIMD), ChaCha20-Poly1305 256.
 static const int kGcmWG = 1024;
 
-#ifndef QPP_CHACHA_WG
-#define QPP_CHACHA_WG 256  // study switch: the ChaCha20-Poly1305 kernel's workgroup size
-#endif
-static const int kChachaWG = QPP_CHACHA_WG;
+static const int kChachaWG = 256;
 
 // GCM blocks per lane per step (gcm_pad): 2 (r2i, same box: north star
 // 1.419 -> 1.389 ms protect, config 4 310 -> 316 GiB/s; WRITE_SIZE 2.08 ->
@@ -3305,10 +3079,7 @@ static const int kChachaWG = QPP_CHACHA_WG;
 // under test); read once per process.
 static int gcm_bpl_choice()
 {
-    static const int b = [] {
-        const char *v = getenv("QPP_GCM_BPL");
-        return (v && atoi(v) == 1) ? 1 : 2;
-    }();
+    static const int b = qpp_env_long("QPP_GCM_BPL", 2) == 1 ? 1 : 2;
     return b;
 }
 
@@ -3317,10 +3088,7 @@ static int gcm_bpl_choice()
 // (a study and test switch, read once per process).
 static bool lone_choice()
 {
-    static const bool b = [] {
-        const char *v = getenv("QPP_LONE");
-        return !(v && v[0] == '0');
-    }();
+    static const bool b = qpp_env_long("QPP_LONE", 1) != 0;
     return b;
 }
 
@@ -3330,15 +3098,9 @@ static bool lone_choice()
 // 4096 packets, 49 against 59 at 8192, 88 against 63 at 16384; ChaCha20
 // 12.9 against 28.9 at 2 packets, then within +-1-3 us of the quad kernel up
 // to 4096 and 47.5 against 30.6 at 8192, so past the host path's small
-// calls the quad kernel's fewer instructions keep it).  QPP_LONE_MAX
-// overrides both (a study switch for tools/lone_sizes.py).
+// calls the quad kernel's fewer instructions keep it).
 static uint32_t lone_max(int suite)
 {
-    static const long env = [] {
-        const char *v = getenv("QPP_LONE_MAX");
-        return v ? atol(v) : -1L;
-    }();
-    if (env >= 0) return (uint32_t)(env > (1 << 20) ? (1 << 20) : env);
     return suite == QPP_CHACHA20_POLY1305 ? 64u : 8192u;
 }
 
@@ -3349,10 +3111,7 @@ static uint32_t lone_max(int suite)
 // (a study and test switch, read once per process).
 static bool zero_copy_choice()
 {
-    static const bool b = [] {
-        const char *v = getenv("QPP_ZERO_COPY");
-        return !(v && v[0] == '0');
-    }();
+    static const bool b = qpp_env_long("QPP_ZERO_COPY", 1) != 0;
     return b;
 }
 
@@ -3361,10 +3120,7 @@ static bool zero_copy_choice()
 // switch, read once per process).
 static bool lone_stage_choice()
 {
-    static const bool b = [] {
-        const char *v = getenv("QPP_LONE_STAGE");
-        return !(v && v[0] == '0');
-    }();
+    static const bool b = qpp_env_long("QPP_LONE_STAGE", 1) != 0;
     return b;
 }
 
@@ -3374,14 +3130,8 @@ static bool lone_stage_choice()
 // paths' QPP_S_INTERNAL reporting can be checked.
 static int apply_spin_env(hipStream_t s)
 {
-    static const long env = [] {
-        const char *v = getenv("QPP_SPIN_LIMIT");
-        return v ? atol(v) : -1L;
-    }();
-    static const long delay = [] {
-        const char *v = getenv("QPP_PAIR_DELAY");  // test switch, g_qpp_pair_delay
-        return v ? atol(v) : -1L;
-    }();
+    static const long env = qpp_env_long("QPP_SPIN_LIMIT", -1);
+    static const long delay = qpp_env_long("QPP_PAIR_DELAY", -1);  // test switch, g_qpp_pair_delay
     if (env < 0 && delay < 0) return QPP_OK;
     static std::atomic<uint64_t> done{0};
     int dev = 0;
@@ -3437,25 +3187,18 @@ static uint32_t gcm_grid(uint32_t items, uint32_t waves_per_wg)
 // single-key launch, its waves drawing pooled chunks of 8 items from a
 // launch-wide counter fetched ahead of need, measured no faster than one of
 // 1024 at the north star, profiles/r4f_ab_pooled.txt.)
-#ifndef QPP_TWO_WG_ITEMS
-#define QPP_TWO_WG_ITEMS 16u  // study switch: items per CU up to which the 512 shape runs
-#endif
+constexpr uint32_t kTwoWgItems = 16;  // items per CU up to which the 512 shape runs: 2 workgroups x 8 waves
 static bool gcm_two_wg(const qpp_keytab *kt, uint32_t suite, uint32_t items)
 {
-    return kt->n_suite[suite] == 1 && items <= cu_count() * (uint32_t)QPP_TWO_WG_ITEMS;  // 2 workgroups x 8 waves per CU
+    return kt->n_suite[suite] == 1 && items <= cu_count() * kTwoWgItems;
 }
 
 // ChaCha20-Poly1305 issue priority by progress (k_chacha PRIO): for launches
 // whose waves all fit the chip at once (kChachaWpe per SIMD, one round), so
-// each SIMD's waves end together instead of oldest first.  QPP_CHACHA_PRIO=0
-// turns it off, =2 forces it on for every launch (A/B switches, read once).
+// each SIMD's waves end together instead of oldest first.
 static bool chacha_prio(uint32_t waves)
 {
-    static const int m = [] {
-        const char *v = getenv("QPP_CHACHA_PRIO");
-        return v ? atoi(v) : 1;
-    }();
-    return m == 2 || (m == 1 && waves <= cu_count() * 4u * kChachaWpe);
+    return waves <= cu_count() * 4u * kChachaWpe;
 }
 
 static int launch_packets(bool enc, const qpp_keytab *kt, const qpp_desc *d_desc, uint32_t n,
@@ -3483,7 +3226,7 @@ static int launch_packets(bool enc, const qpp_keytab *kt, const qpp_desc *d_desc
 #define QPP_LAUNCH_GCM_W(SUITE, BPLV, WGV, CLDSV)                                              \
     do {                                                                                       \
         const dim3 grid(gcm_grid(waves, WGV / 64)), block(WGV);                                 \
-        const int psl = (WGV == 1024 || QPP_POOL512) && kt->n_suite[SUITE] == 1 ? pool_acquire(kt) : -1; \
+        const int psl = WGV == 1024 && kt->n_suite[SUITE] == 1 ? pool_acquire(kt) : -1;        \
         uint32_t *pl = psl >= 0 ? kt->pool->d + (size_t)psl * kPoolStride : nullptr;          \
         if (CLDSV) g_close_lds_launches.fetch_add(1, std::memory_order_relaxed);               \
         if (enc)                                                                               \
@@ -3531,11 +3274,7 @@ static int launch_packets(bool enc, const qpp_keytab *kt, const qpp_desc *d_desc
                                d_out, d_res, lst);
         HIPCHK(hipGetLastError());
     } else if (mask & (1u << QPP_CHACHA20_POLY1305)) {
-        uint32_t cgrid = (waves + kChachaWG / 64 - 1) / (kChachaWG / 64);
-        if (QPP_CH_PERSIST > 0) {  // study: at most QPP_CH_PERSIST rounds of resident workgroups
-            const uint32_t resident = cu_count() * (uint32_t)(4 * kChachaWpe / (kChachaWG / 64)) * (uint32_t)QPP_CH_PERSIST;
-            cgrid = cgrid < resident ? cgrid : resident;
-        }
+        const uint32_t cgrid = (waves + kChachaWG / 64 - 1) / (kChachaWG / 64);
         const dim3 grid(cgrid ? cgrid : 1u), block(kChachaWG);
         if (chacha_prio(waves)) {
             if (enc)
@@ -3745,14 +3484,10 @@ void *qpp_session_stream(qpp_session *s) { return s ? (void *)s->stream : NULL; 
 // Host copies between caller memory and pinned staging with non-temporal
 // stores: a plain memcpy below glibc's non-temporal threshold reads each
 // destination line before writing it (write-allocate), so a copy moves three
-// times its size through host memory instead of two.  QPP_COPY_NT=0 (a study
-// switch, read once per process) keeps memcpy.
+// times its size through host memory instead of two.  (memcpy without AVX2.)
 static bool copy_nt_choice()
 {
-    static const bool b = [] {
-        const char *v = getenv("QPP_COPY_NT");
-        return !(v && v[0] == '0') && __builtin_cpu_supports("avx2");
-    }();
+    static const bool b = __builtin_cpu_supports("avx2");
     return b;
 }
 
@@ -3797,6 +3532,7 @@ struct CopyGroup {
     }
 };
 
+constexpr int kCopyThreads = 6;  // 2, 3, 4, 8 and 12 measured within the spread of 6
 class CopyPool {
   public:
     static CopyPool &get()
@@ -3839,9 +3575,6 @@ class CopyPool {
     };
     CopyPool()
     {
-        const char *v = getenv("QPP_COPY_THREADS");  // A/B switch, default 6
-        const int t = v ? atoi(v) : 6;
-        n_ = t < 1 ? 1 : t > 32 ? 32 : t;
         // (round 5 also pinned the threads to the CPUs of the device's NUMA
         // node: 13.0-16.6 against 11.5-17.7 GiB/s unpinned on one two-socket
         // box, interleaved -- no difference through the run-to-run spread,
@@ -3873,7 +3606,7 @@ class CopyPool {
             }
         }
     }
-    int n_ = 8;
+    const int n_ = kCopyThreads;
     std::mutex mu_;
     std::condition_variable cv_;
     std::deque<Task> q_;
@@ -3948,64 +3681,20 @@ static int session_launch(bool enc, qpp_session *s, const qpp_keytab *kt, const 
 }
 
 // D2H of a session: up to two device ranges into pinned host memory (device
-// views), by k_xfer.  QPP_D2H_KERNEL=0 (a study switch, read once per
-// process) uses hipMemcpyAsync on the stream instead.
-static bool d2h_kernel_choice()
-{
-    static const bool b = [] {
-        const char *v = getenv("QPP_D2H_KERNEL");
-        return !(v && v[0] == '0');
-    }();
-    return b;
-}
-
+// views), by k_xfer.
 static int launch_xfer(uint8_t *d0, const uint8_t *s0, size_t n0, uint8_t *d1, const uint8_t *s1, size_t n1,
                        hipStream_t st)
 {
     if (!n0 && !n1) return QPP_OK;
     const size_t units = (std::max(n0, n1) + 15) / 16;
-    // ~8 16-byte units per thread, at most xfer_wgs() workgroups per range
-    static const size_t cap = [] {
-        const char *v = getenv("QPP_XFER_WGS");  // study switch, read once per process
-        const long c = v ? atol(v) : 1024;
-        return (size_t)(c < 1 ? 1 : c > 4096 ? 4096 : c);
-    }();
+    // ~8 16-byte units per thread, at most 1024 workgroups per range
+    constexpr size_t cap = 1024;
     size_t g = (units + (size_t)kXferWG * 8 - 1) / ((size_t)kXferWG * 8);
     if (g < 1) g = 1;
     if (g > cap) g = cap;
     hipLaunchKernelGGL(k_xfer, dim3((uint32_t)g, n1 ? 2u : 1u), dim3(kXferWG), 0, st, s0, d0, n0, s1, d1, n1);
     HIPCHK(hipGetLastError());
     return QPP_OK;
-}
-
-static int session_d2h(uint8_t *h0, uint8_t *hd0, const uint8_t *s0, size_t n0, uint8_t *h1, uint8_t *hd1,
-                       const uint8_t *s1, size_t n1, hipStream_t st)
-{
-    if (!d2h_kernel_choice()) {
-        if (n0) HIPCHK(hipMemcpyAsync(h0, s0, n0, hipMemcpyDeviceToHost, st));
-        if (n1) HIPCHK(hipMemcpyAsync(h1, s1, n1, hipMemcpyDeviceToHost, st));
-        return QPP_OK;
-    }
-    return launch_xfer(hd0, s0, n0, hd1, s1, n1, st);
-}
-
-// QPP_H2D_KERNEL=1 (a study switch, read once per process): the pipelined
-// session's H2D legs by k_xfer too (default: hipMemcpyAsync, the copy engines)
-static bool h2d_kernel_choice()
-{
-    static const bool b = [] {
-        const char *v = getenv("QPP_H2D_KERNEL");
-        return v && v[0] == '1';
-    }();
-    return b;
-}
-
-// QPP_SESSION_TRACE=1: one stderr line per pipelined call with its host
-// phases (a study switch, read once per process)
-static bool trace_on()
-{
-    static const bool b = getenv("QPP_SESSION_TRACE") != nullptr;
-    return b;
 }
 
 // Chunk c of the batch: its descriptors are copied into pinned staging and
@@ -4082,8 +3771,7 @@ static int session_run_pipelined(bool enc, qpp_session *s, const qpp_keytab *kt,
         memcpy(hd + a, desc + a, (size_t)(b - a) * sizeof(qpp_desc));
         reject_out_of_bounds(enc, hd + a, b - a, in_len, out_len);
         if (tr) HIPCHK(hipEventRecord(s->tev[0][c], sin));
-        const bool h2dk = h2d_kernel_choice();
-        if (b > a && !h2dk)
+        if (b > a)
             HIPCHK(hipMemcpyAsync(dd + a, hd + a, (size_t)(b - a) * sizeof(qpp_desc), hipMemcpyHostToDevice,
                                   sin));
         size_t lo = SIZE_MAX, hi = 0;
@@ -4101,14 +3789,8 @@ static int session_run_pipelined(bool enc, qpp_session *s, const qpp_keytab *kt,
                 par_memcpy(s->h_in + lo, in + lo, hi - lo);
                 if (tr) t_copy_in += clk() - t0;
             }
-            if (!h2dk) HIPCHK(hipMemcpyAsync(s->d_in + lo, s->h_in + lo, hi - lo, hipMemcpyHostToDevice, sin));
+            HIPCHK(hipMemcpyAsync(s->d_in + lo, s->h_in + lo, hi - lo, hipMemcpyHostToDevice, sin));
             in_bytes += (double)(hi - lo);
-        }
-        if (h2dk) {
-            rc = launch_xfer((uint8_t *)(dd + a), s->hd_misc + (size_t)a * sizeof(qpp_desc),
-                             (size_t)(b - a) * sizeof(qpp_desc), lo < hi ? s->d_in + lo : nullptr,
-                             lo < hi ? s->hd_in + lo : nullptr, lo < hi ? hi - lo : 0, sin);
-            if (rc != QPP_OK) break;
         }
         in_bytes += (double)(b - a) * sizeof(qpp_desc);
         HIPCHK(hipEventRecord(s->ev_in[c], sin));
@@ -4127,8 +3809,8 @@ static int session_run_pipelined(bool enc, qpp_session *s, const qpp_keytab *kt,
         {
             const size_t tl = olo[c + 1] > olo[c] ? olo[c + 1] - olo[c] : 0;
             const size_t rl = (size_t)(b - a) * sizeof(qpp_result);
-            rc = session_d2h(s->h_out + olo[c], s->hd_out + olo[c], s->d_out + olo[c], tl, (uint8_t *)(hr + a),
-                             (uint8_t *)(hrd + a), (const uint8_t *)(dr + a), rl, s->s_out);
+            rc = launch_xfer(s->hd_out + olo[c], s->d_out + olo[c], tl, (uint8_t *)(hrd + a),
+                             (const uint8_t *)(dr + a), rl, s->s_out);
             if (rc != QPP_OK) break;
         }
         HIPCHK(hipEventRecord(s->ev_out[c], s->s_out));
@@ -4144,7 +3826,6 @@ static int session_run_pipelined(bool enc, qpp_session *s, const qpp_keytab *kt,
     }
     if (rc != QPP_OK) return rc;
     const double t_sub = clk();
-    const int early = next_out;
     for (int c = next_out; c < chunks; ++c) {
         HIPCHK(hipEventSynchronize(s->ev_out[c]));
         hand_back(c);
@@ -4176,10 +3857,6 @@ static int session_run_pipelined(bool enc, qpp_session *s, const qpp_keytab *kt,
         HIPCHK(hipEventElapsedTime(&ms, s->tev[0][0], s->tev[5][chunks - 1]));
         T.gpu_span_ms = ms;
     }
-    if (trace_on())
-        fprintf(stderr, "qpp session: %s %u packets %d chunks in %d out %d: submit %.2f ms, wait %.2f ms (%d handed back early)\n",
-                enc ? "protect" : "unprotect", n, chunks, (int)in_direct, (int)out_direct,
-                t_sub - t_start, t_end - t_sub, early);
     return QPP_OK;
 }
 
@@ -4212,8 +3889,8 @@ static int session_run(bool enc, qpp_session *s, const qpp_keytab *kt, const qpp
     size_t want = out_len / kPipeChunkBytes;
     int chunks = want > (size_t)kPipeRegular ? kPipeRegular : (int)want;
     if (chunks > (int)n) chunks = (int)n;
-    const char *serial = getenv("QPP_SESSION_SERIAL");  // A/B switch: "1" = serial path
-    if (chunks >= 2 && !(serial && serial[0] == '1')) {
+    // QPP_SESSION_SERIAL=1 (an A/B and test switch, read at every call): the serial path
+    if (chunks >= 2 && qpp_env_long("QPP_SESSION_SERIAL", 0) != 1) {
         bool mono = true;
         for (uint32_t i = 1; i < n && mono; ++i) mono = desc[i].out_off >= desc[i - 1].out_off;
         if (mono)
@@ -4280,9 +3957,8 @@ static int session_run(bool enc, qpp_session *s, const qpp_keytab *kt, const qpp
     if (out_len) HIPCHK(hipMemsetAsync(s->d_out, 0, out_len, s->stream));
     rc = session_launch(enc, s, kt, dd, n, dr);
     if (rc != QPP_OK) return rc;
-    rc = session_d2h(s->h_out, s->hd_out, s->d_out, out_len, (uint8_t *)hr,
-                     s->hd_misc + (size_t)s->max_packets * sizeof(qpp_desc), (const uint8_t *)dr,
-                     (size_t)n * sizeof(qpp_result), s->stream);
+    rc = launch_xfer(s->hd_out, s->d_out, out_len, s->hd_misc + (size_t)s->max_packets * sizeof(qpp_desc),
+                     (const uint8_t *)dr, (size_t)n * sizeof(qpp_result), s->stream);
     if (rc != QPP_OK) return rc;
     HIPCHK(hipStreamSynchronize(s->stream));
     if (out_len && out != s->h_out) memcpy(out, s->h_out, out_len);

@@ -7,6 +7,15 @@
 
 #include "qpp_device.h"
 
+// The one way the library reads an environment switch: the variable's integer
+// value, or dflt when it is unset or empty.  Every switch is a product or
+// test switch that some test drives (tests/test_switches.py keeps the list).
+static inline long qpp_env_long(const char *name, long dflt)
+{
+    const char *v = getenv(name);
+    return (v && *v) ? atol(v) : dflt;
+}
+
 // A batch's bucketing (quic_pp.h, qpp_plan_*): device buffers for n <= cap.
 struct qpp_plan {
     uint32_t cap;

@@ -384,7 +384,8 @@ int qpp_internal_plan_build(qpp_plan *p, const KeySlot *d_slots, uint32_t cap, c
     if (hipMemsetAsync(p->d_count, 0, 32 * sizeof(uint32_t), s) != hipSuccess) return QPP_E_HIP;
     const int sb = bits_for(cap);
     const dim3 grid((n + kPlanWG - 1) / kPlanWG);
-    if (n && cap <= kPlanCountSlots && getenv("QPP_PLAN_RADIX") == nullptr) {
+    // QPP_PLAN_RADIX=1 (a test switch, read at every build): the radix sort for small tables too
+    if (n && cap <= kPlanCountSlots && qpp_env_long("QPP_PLAN_RADIX", 0) == 0) {
         const uint32_t nb = 4u << sb;
         if (hipMemsetAsync(p->d_bins, 0, nb * 4, s) != hipSuccess) return QPP_E_HIP;
         const dim3 cgrid((n + kCntPer * kScanWG - 1) / (kCntPer * kScanWG));

@@ -393,7 +393,6 @@ def lengths_check(path, suite, form, tag=""):
     lone_on = (env("QPP_LONE") or "1")[0] != "0"
     bpl1 = env("QPP_GCM_BPL") == "1"
     # the launcher's rules this form relies on (launch_packets): the switches are as the form needs them
-    assert env("QPP_LONE_MAX") is None and env("QPP_CHACHA_PRIO") is None
     if form in ("lone", "pair", "lone64"):
         assert lone_on and n <= LONE_MAX and (suite == 2) == (form == "lone64")
     if form == "prio":

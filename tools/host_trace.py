@@ -45,5 +45,5 @@ for rep in range(reps):
               f"({gbs(t['in_bytes'], t['h2d_ms']):4.1f} GB/s) kern {t['kernel_ms']:4.1f} d2h {t['d2h_ms']:5.1f} "
               f"({gbs(t['out_bytes'], t['d2h_ms']):4.1f} GB/s) span {t['gpu_span_ms']:5.1f}", flush=True)
 ok = bool((r1["status"] == 0).all() and (r2["status"] == 0).all() and np.array_equal(back, plain))
-print(json.dumps({"threads": os.environ.get("QPP_COPY_THREADS", "6"), "round_trip_gib_s": [round(x, 2) for x in rts],
+print(json.dumps({"threads": "6", "round_trip_gib_s": [round(x, 2) for x in rts],
                   "median": round(sorted(rts)[len(rts) // 2], 2), "ok": ok}), flush=True)
