@@ -641,7 +641,12 @@ __device__ __forceinline__ u32x4 gcm_packet(const Pkt &P, const KeySlot *ks, con
     const bool tiny = rlen < 16;
     // the H^4 entry, read once: an LDS read inside the step loop would make
     // every step wait for all of its outstanding table lookups
-    const uint32_t t4 = G.t4();
+    // (CLDS: the workgroup's one entry, at a compile-time address)
+    const uint32_t t4 = CLDS ? 0u : G.t4();
+    auto mul_h4 = [&](u32x4 x) -> u32x4 {
+        if constexpr (CLDS) return ghash_mul_lds5c(x, G.lds);
+        else return ghash_mul_h4(x, G.lds, t4);
+    };
     const u32x4 tiny_in = tiny ? ld_part(P.src, rlen) : zero4();
     const int q = pad + za;  // sequence position of CT block 0
     const uint32_t cin = ioff + (uint32_t)hlen, cout = ooff + (uint32_t)hlen;
@@ -745,7 +750,7 @@ __device__ __forceinline__ u32x4 gcm_packet(const Pkt &P, const KeySlot *ks, con
         acc ^= blk_out(i, ksb, raw);
         __builtin_amdgcn_sched_barrier(0);
         // H^4 inside the loop (resident LDS table); the last step closes
-        if (!last) acc = ghash_mul_h4(acc, G.lds, t4);
+        if (!last) acc = mul_h4(acc);
         else close(ksb);
     };
     // BPL = 2: lane blocks i and i + 4 (CT indices) in one step
@@ -790,8 +795,8 @@ __device__ __forceinline__ u32x4 gcm_packet(const Pkt &P, const KeySlot *ks, con
         __builtin_amdgcn_sched_barrier(0);
         // (0 ^ 0) H^4 = 0 over front padding
         if (first && pad >= 4) acc = x1;
-        else acc = ghash_mul_h4(acc ^ x0, G.lds, t4) ^ x1;
-        if (!last) acc = ghash_mul_h4(acc, G.lds, t4);
+        else acc = mul_h4(acc ^ x0) ^ x1;
+        if (!last) acc = mul_h4(acc);
         else close(ks1);
     };
     got_tag = u32x4{0, 0, 0, 0};
@@ -1508,6 +1513,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
     const uint32_t sb = ib + min(stat, per * blockIdx.x), se = ib + min(stat, per * (blockIdx.x + 1));
     if (!pool && sb >= se) return;  // uniform over the workgroup
     static_assert(!CLDS || WG == 1024, "the 512-thread shape has no LDS to spare for the close tables");
+    static_assert(!CLDS || gcm_tab_entries<WG, CLDS>() == 1, "gcm_packet<CLDS> reads the H^4 table at entry 0");
     __shared__ GcmSmem<WG, CLDS> sm;
     // Thread-derived values are recomputed where they are used, from the
     // wave index (an SGPR) and a fresh lane id, instead of being kept live
@@ -2492,17 +2498,14 @@ __global__ __launch_bounds__(kSetupWG) void k_key_setup(KeySlot *__restrict__ sl
         uint32_t *t5 = (uint32_t *)(gtab + (size_t)m.slot * kGhashTabBytes + kGh5Off);
         for (int i = threadIdx.x; i < kGh5Windows * 32; i += kSetupWG) {
             const int w = i >> 5, e = i & 31;
-            uint32_t words[4] = {0, 0, 0, 0};
-            for (int b = 0; b < 5; ++b) {
-                const int bit = 5 * w + b;
-                if (bit < 128 && ((e >> b) & 1)) words[bit >> 5] |= 1u << (bit & 31);
-            }
+            uint32_t words[4];
+            gh5_element(w, (uint32_t)e, words);
             const u32x4 v = gf128_mul_slow(u32x4{words[0], words[1], words[2], words[3]}, hpow[3]);
-            uint32_t *row = t5 + w * 64, *rhi = t5 + (kGh5Hi / 4) + w * 64;
-            row[2 * e] = v.x;
-            row[2 * e + 1] = v.y;
-            rhi[2 * e] = v.z;
-            rhi[2 * e + 1] = v.w;
+            uint32_t *lo = t5 + gh5_word(w, (uint32_t)e), *hi = lo + kGh5Hi / 4;
+            lo[0] = v.x;
+            lo[1] = v.y;
+            hi[0] = v.z;
+            hi[1] = v.w;
         }
     }
 }
