@@ -77,8 +77,8 @@ class KeySlots:
     until their context lets them go: CryptoContext.teardown and a key update
     (apply_key_phase) release them here (``release``), which frees the slot
     and clears its device entry, as the reference drops its EVP contexts.
-    When the table is full it is cleared and refilled; that happens only
-    between launches.
+    When the table is full it is cleared, on the device too, and refilled;
+    that happens only between launches.
 
     Like the reference's AEAD objects, a KeySlots is not meant to be shared
     by threads; the batched callers' default table is one per thread.  A
@@ -129,6 +129,14 @@ class KeySlots:
         self._by_obj.clear()
         self._pending.clear()
 
+    def _refill(self) -> None:
+        """The table is full: clear the device entry of every slot held, then
+        forget them all, so no slot keeps a key that nothing is bound to."""
+        held = sorted(self._keep)
+        if held:
+            self.table.clear(np.asarray(held, np.uint32).tobytes())
+        self.reset()
+
     def commit(self) -> None:
         """Install the slots added since the last commit (one launch)."""
         if self._inbox:
@@ -144,7 +152,7 @@ class KeySlots:
         try:
             slots = [self.slot_for(*t) for t in triples]
         except OverflowError:
-            self.reset()
+            self._refill()
             uniq = {(id(a), id(h), int(k)) for a, h, k in triples}
             if len(uniq) > self.capacity:
                 raise
@@ -162,7 +170,7 @@ class KeySlots:
         if n > self.capacity:
             raise OverflowError("key table full")
         if n > self.capacity - len(self._keep):
-            self.reset()
+            self._refill()
         high = len(self._keep) + len(self._free)
         take = self._free[::-1][:n]
         return take + list(range(high, high + n - len(take)))
@@ -222,10 +230,7 @@ class KeySlots:
         """The owner is done with the table: apply queued releases, then
         clear every device entry still held and drop the held objects."""
         self._drain()
-        held = sorted(self._keep)
-        if held:
-            self.table.clear(np.asarray(held, np.uint32).tobytes())
-        self.reset()
+        self._refill()
 
 
 # every live KeySlots, so that a context's teardown can release its keys;

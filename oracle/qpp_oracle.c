@@ -516,9 +516,11 @@ void qo_protect_batch(const qpp_key_material *keys, uint32_t n_keys, const qpp_d
         const qpp_desc *d = &desc[i];
         qpp_result *r = &res[i];
         r->pn = d->pn;
-        r->hdr_len = d->hdr_len;
+        r->hdr_len = 0;
         r->out_len = 0;
+        /* no key: nothing of the packet is looked at, in either direction */
         if (!slot_ok(keys, n_keys, d->slot)) { r->status = QPP_S_NO_KEY; continue; }
+        r->hdr_len = d->hdr_len;
         const qpp_key_material *k = &keys[d->slot];
         const uint8_t *hdr = in + d->in_off, *pl = hdr + d->hdr_len;
         uint8_t *o = out + d->out_off;

@@ -329,6 +329,16 @@ def test_setup_initial_batch():
     t = CryptoPair()
     t.setup_initial(bytes([29]) * 8, False, V2)
     assert _ctx_state(more[29].send) == _ctx_state(t.send) and _ctx_state(more[29].recv) == _ctx_state(t.recv)
+    # the refill left no key behind: the slots held before and not bound again are empty on the
+    # device, the ones bound again hold keys (one launch over slots 0..79)
+    assert sorted(ks._keep) == list(range(60))
+    hdr, payload = short_header(b"\x66" * 8, 1, 2, 0), bytes(40)
+    probe = np.zeros(80, dtype=L.DESC)
+    probe["in_off"] = probe["out_off"] = 128 * np.arange(80)
+    probe["len"], probe["hdr_len"], probe["pn"], probe["slot"] = 40, len(hdr), 1, np.arange(80)
+    _, res = _crypto.protect_host(ks.table, probe.tobytes(), (hdr + payload).ljust(128, b"\0") * 80, 128 * 80)
+    status = np.frombuffer(res, dtype=L.RESULT)["status"]
+    assert (status[:60] == L.S_OK).all() and (status[60:] == L.S_NO_KEY).all()
     with pytest.raises(ValueError):
         setup_initial_batch(more[30:31], [bytes(21)], False, 1, slots=ks)
     ks.close()

@@ -362,6 +362,94 @@ def test_key_slots_release_on_teardown_and_update():
     assert len(slots._keep) == 1
 
 
+def _protect_on_slots(table, n_slots, pn=5):
+    """One short-header packet per slot 0..n_slots-1 through `table`
+    (protect_host): the wire images (None where the status is not S_OK) and
+    the statuses; plus the header and payload used."""
+    from aioquic_amd._crypto import protect_host
+
+    hdr, payload = bytes([0x41]) + bytes(range(8)) + bytes([0, pn]), bytes(range(1, 41))
+    size = len(hdr) + len(payload) + 16
+    desc = np.zeros(n_slots, dtype=L.DESC)
+    desc["in_off"] = desc["out_off"] = 128 * np.arange(n_slots)
+    desc["len"], desc["hdr_len"], desc["pn"], desc["slot"] = len(payload), len(hdr), pn, np.arange(n_slots)
+    data = bytearray(128 * n_slots)
+    for s in range(n_slots):
+        data[128 * s: 128 * s + len(hdr) + len(payload)] = hdr + payload
+    out, res = protect_host(table, desc.tobytes(), bytes(data), 128 * n_slots)
+    res = np.frombuffer(res, dtype=L.RESULT)
+    wires = [bytes(out[128 * s: 128 * s + size]) if res[s]["status"] == L.S_OK else None for s in range(n_slots)]
+    return wires, res["status"].tolist(), hdr, payload
+
+
+@pytest.mark.gpu
+def test_key_slots_refill_leaves_no_key_behind(oracle):
+    """A full table is cleared and refilled (KeySlots.assign, .reserve): every
+    slot that is not bound again reports KeyUnavailable on the device, as the
+    reference drops its EVP contexts, and the slots bound again protect
+    exactly like a fresh table's (and like the oracle)."""
+    from tests.golden_cases import gen_bytes
+
+    from aioquic_amd.batch_io import KeySlots
+
+    def ctx(tag, suite):
+        kl = 16 if suite == L.AES_128_GCM else 32
+        return _Ctx(suite, gen_bytes(tag + "-key", kl), gen_bytes(tag + "-iv", 12), gen_bytes(tag + "-hp", kl))
+
+    def triple(c):
+        return (c.aead, c.hp, c.key_phase)
+
+    def want(c, hdr, payload, pn=5):
+        suite, key, iv = c.aead._material()
+        return oracle.protect(suite, key, iv, c.hp._material()[1], hdr, payload, pn)
+
+    four = [ctx("refill-%d" % k, (L.AES_128_GCM, L.CHACHA20_POLY1305)[k & 1]) for k in range(4)]
+    fifth = ctx("refill-4", L.AES_128_GCM)
+
+    # assign(): the fifth key overflows the table; it and one old key are bound again
+    slots = KeySlots(4)
+    assert slots.assign([triple(c) for c in four]) == [0, 1, 2, 3]
+    wires, status, hdr, payload = _protect_on_slots(slots.table, 4)
+    assert status == [L.S_OK] * 4 and wires == [want(c, hdr, payload) for c in four]
+    assert slots.assign([triple(fifth), triple(four[1])]) == [0, 1]
+    assert len(slots._keep) == 2 and not slots._free and not slots._pending
+    wires, status, _, _ = _protect_on_slots(slots.table, 4)
+    assert status == [L.S_OK, L.S_OK, L.S_NO_KEY, L.S_NO_KEY]
+    fresh = KeySlots(4)
+    assert fresh.assign([triple(fifth), triple(four[1])]) == [0, 1]
+    fwires, fstatus, _, _ = _protect_on_slots(fresh.table, 4)
+    assert fstatus == status and fwires == wires
+    assert wires[:2] == [want(fifth, hdr, payload), want(four[1], hdr, payload)]
+    # the single AES-128 key left has its suite to itself again, and the table goes on working
+    assert slots.assign([triple(four[3])]) == [2]
+    wires, status, _, _ = _protect_on_slots(slots.table, 4)
+    assert status == [L.S_OK, L.S_OK, L.S_OK, L.S_NO_KEY] and wires[2] == want(four[3], hdr, payload)
+    slots.close()
+    fresh.close()
+    assert _protect_on_slots(slots.table, 4)[1] == [L.S_NO_KEY] * 4
+
+    # reserve() + adopt(): two slots for keys the caller derives on the table itself
+    slots = KeySlots(4)
+    assert slots.assign([triple(c) for c in four]) == [0, 1, 2, 3]
+    taken = slots.reserve(2)
+    assert taken == [0, 1] and not slots._keep
+    cid = gen_bytes("refill-cid", 8)
+    slots.table.derive_initial(L.initial_record(taken[0], taken[1], cid).tobytes())
+    ends = []
+    for secret in oracle.initial_secrets(cid):
+        key, iv, hp = oracle.derive_key_iv_hp(L.AES_128_GCM, secret)
+        ends.append(_Ctx(L.AES_128_GCM, key, iv, hp))
+    slots.adopt(taken, [triple(c) for c in ends])
+    assert sorted(slots._keep) == [0, 1] and not slots._pending
+    wires, status, _, _ = _protect_on_slots(slots.table, 4)
+    assert status == [L.S_OK, L.S_OK, L.S_NO_KEY, L.S_NO_KEY]
+    assert wires[:2] == [want(c, hdr, payload) for c in ends]
+    # the adopted slots are found again, and nothing is installed twice
+    assert slots.assign([triple(ends[1]), triple(ends[0])]) == [1, 0] and not slots._pending
+    slots.close()
+    assert _protect_on_slots(slots.table, 4)[1] == [L.S_NO_KEY] * 4
+
+
 @pytest.mark.gpu
 def test_key_release_from_another_thread_is_queued():
     """A context torn down on another thread does not touch this thread's
