@@ -18,6 +18,9 @@
 //   * ChaCha20-Poly1305: lane j owns 64-byte chunks c = 4k + j; Poly1305 by
 //     per-lane Horner (r per block, r^12 more between chunks) and one DPP sum.
 //   * No MFMA: the work is byte/bit arithmetic, bound by LDS and VALU issue.
+// After the kernels: the key table and the device-buffer C ABI that launches
+// them (launch_packets).  The host-buffer path -- qpp_session, qpp_multi -- is
+// qpp_session.hip, which reaches this file through qpp_internal.h only.
 #include <hip/hip_runtime.h>
 
 #include "qpp_chacha.h"
@@ -43,10 +46,7 @@ constexpr int kSetupWG = 256;
 constexpr int kScratch = 112;
 constexpr int kScrEj0 = 48, kScrPark = 64, kScrHdr = 96;
 constexpr uint32_t kNoSlot = 0xffffffffu;
-// Descriptor flag set by the host session for a descriptor whose extents do
-// not fit the caller's buffers: the packet reports QPP_S_LENGTH and no byte
-// of it is read or written.
-constexpr uint32_t kFlagReject = 0x8000u;
+// (kFlagReject, the host session's "does not fit the caller's buffers": qpp_batch.h)
 // ChaCha20-Poly1305: minimum waves per SIMD (4: 128 VGPRs, 8 spilled; r2i
 // same box against 1 (146 VGPRs, 3 waves): 64 Ki +4 %, 1 Mi +1 %, config 5 +1 %)
 constexpr int kChachaWpe = 4;
@@ -1860,21 +1860,8 @@ __global__ __launch_bounds__(WG, kChachaWpe) void k_chacha(const KeySlot *__rest
 // Launches stay latency-bound up to a few thousand packets (one workgroup
 // of 16 packets per CU), so unplanned launches up to lone_max take these
 // kernels; past that the quad kernels' ~7x fewer instructions per packet win.
-constexpr int kLoneWG = 1024;      // 16 packets per workgroup, one AES image
-
-// A small host call handed to a lone kernel whole (qpp_session): the kernel
-// copies the call's descriptors and input from the pinned staging (src, its
-// device view) into the device staging (dst) itself, every thread 16 bytes
-// in one bus round trip, instead of a copy-engine blit scheduled between
-// stream operations.  bytes == 0: nothing staged (device-buffer launches).
-// One workgroup (at most 16 packets); the workgroup barrier makes the copy
-// visible to its waves (vector L1 writes through to L2).
-struct LoneStage {
-    const uint8_t *src;
-    uint8_t *dst;
-    uint32_t bytes;  // multiple of 16, <= kLoneStageMax
-};
-constexpr uint32_t kLoneStageMax = 2 * kLoneWG * 16;
+// (kLoneWG = 1024, 16 packets per workgroup, and LoneStage, a small host call
+// staged by the kernel itself: qpp_internal.h)
 
 __device__ __forceinline__ void lone_stage_load(const LoneStage &st, u32x4 &a, u32x4 &b)
 {
@@ -2637,16 +2624,9 @@ __global__ __launch_bounds__(kXferWG) void k_xfer(const uint8_t *__restrict__ s0
 #include <string.h>
 
 #include <algorithm>
-#include <immintrin.h>
-#include <pthread.h>
-
 #include <atomic>
-#include <chrono>
-#include <condition_variable>
-#include <deque>
 #include <mutex>
-#include <thread>
-#include <vector>
+#include <new>
 
 using namespace qpp;
 
@@ -2753,51 +2733,6 @@ static uint32_t keytab_suite_mask(const qpp_keytab *kt)
         if (kt->n_suite[s]) m |= 1u << s;
     return m;
 }
-
-// Host batches of at least 2 x kPipeChunkBytes of output go through the
-// session as a three-stage pipeline of up to kPipeMaxChunks chunks (see
-// session_run_pipelined): up to kPipeRegular chunks of about equal size, the
-// first and last of them cut into quarter, quarter and half (kPipeTaper) so
-// the pipeline fills and drains on small pieces.
-constexpr size_t kPipeChunkBytes = (size_t)32 << 20;
-constexpr int kPipeRegular = 32, kPipeTaper = 2;
-constexpr int kPipeMaxChunks = kPipeRegular + 2 * kPipeTaper;
-constexpr int kMultiMaxDevices = 16;  // qpp_multi: devices per host-batch engine
-
-struct qpp_session {
-    hipStream_t stream;             // kernels (and everything of the serial path)
-    hipStream_t s_in, s_out;        // pipelined path: H2D and D2H copy streams
-    hipEvent_t ev_in[kPipeMaxChunks], ev_k[kPipeMaxChunks], ev_out[kPipeMaxChunks];
-    int device;
-    size_t max_bytes;
-    uint32_t max_packets;
-    uint8_t *h_in, *h_out, *h_misc;  // pinned
-    uint8_t *hd_in, *hd_out, *hd_misc;  // their device views (zero-copy small calls)
-    uint8_t *d_in, *d_out, *d_misc;
-    size_t misc_bytes;
-    qpp_plan *plan;                  // bucketing of batches of >= kSessionPlanMin packets
-    // qpp_session_trace: timing events around every chunk's H2D, kernels and
-    // D2H (start / end), created on first enable; the last traced call
-    bool trace;
-    hipEvent_t tev[6][kPipeMaxChunks];
-    qpp_trace last;
-    // qpp_session_route_unprotect (qpp_route.hip): the small arrays of a routed
-    // batch, apart from the staging above, which a caller may have filled
-    uint8_t *h_scratch, *d_scratch;  // pinned / device
-    size_t scratch_bytes;
-};
-
-// Host batches of at least this many packets are bucketed by (suite, slot)
-// on the device before launch (qpp_plan); smaller ones launch as given.
-constexpr uint32_t kSessionPlanMin = 128;
-
-#define HIPCHK(x)                          \
-    do {                                   \
-        if ((x) != hipSuccess) {           \
-            (void)hipGetLastError();       \
-            return QPP_E_HIP;              \
-        }                                  \
-    } while (0)
 
 extern "C" {
 
@@ -3070,6 +3005,8 @@ int qpp_keytab_clear(qpp_keytab *kt, const uint32_t *slots, uint32_t n, void *st
     return e == hipSuccess ? QPP_OK : QPP_E_HIP;
 }
 
+}  // extern "C" (the launches below have their linkage from quic_pp.h's declarations)
+
 // Workgroup sizes (tuned on MI355X, tools/sweep_wg.sh): GCM 1024 (one
 // persistent workgroup per CU, 4 waves per SIMD), ChaCha20-Poly1305 256.
 static const int kGcmWG = 1024;
@@ -3107,24 +3044,9 @@ static uint32_t lone_max(int suite)
     return suite == QPP_CHACHA20_POLY1305 ? 64u : 8192u;
 }
 
-// Small host calls on the lone-packet kernels (and small header-protection
-// mask calls) read and write the session's pinned staging from the kernel
-// instead of through two copy-engine blits (~3.8 us each plus their
-// scheduling, profiles/r4j_lone_latency); QPP_ZERO_COPY=0 keeps the copies
-// (a study and test switch, read once per process).
-static bool zero_copy_choice()
+uint32_t qpp_internal_lone_limit()
 {
-    static const bool b = qpp_env_long("QPP_ZERO_COPY", 1) != 0;
-    return b;
-}
-
-// A small host call of one workgroup's packets staged by the lone kernel
-// itself instead of a copy (QPP_LONE_STAGE=0: the copy; a study and test
-// switch, read once per process).
-static bool lone_stage_choice()
-{
-    static const bool b = qpp_env_long("QPP_LONE_STAGE", 1) != 0;
-    return b;
+    return lone_choice() ? std::min(lone_max(QPP_AES_128_GCM), lone_max(QPP_CHACHA20_POLY1305)) : 0u;
 }
 
 // QPP_SPIN_LIMIT (a test switch, read once per process) replaces the bounded
@@ -3204,9 +3126,72 @@ static bool chacha_prio(uint32_t waves)
     return waves <= cu_count() * 4u * kChachaWpe;
 }
 
-static int launch_packets(bool enc, const qpp_keytab *kt, const qpp_desc *d_desc, uint32_t n,
-                          const uint8_t *d_in, uint8_t *d_out, qpp_result *d_res, void *stream,
-                          const qpp_plan *plan = nullptr, const LoneStage *stage = nullptr)
+// What the kernels of one launch_packets call are given.
+struct PacketLaunch {
+    bool enc;
+    const qpp_keytab *kt;
+    const qpp_desc *d_desc;
+    uint32_t n;
+    const uint8_t *d_in;
+    uint8_t *d_out;
+    qpp_result *d_res;
+    hipStream_t s;
+    bool planned;
+    const uint32_t *d_items, *d_irange;  // planned: the wave items and each bucket's range of them
+    uint32_t waves;
+    int bpl_gcm;
+    bool lone;
+    LoneStage lst;
+};
+
+// The protect (kp) or the unprotect (ku) instance of a kernel.
+template <typename... P, typename... A>
+static void launch_dir(bool enc, void (*kp)(P...), void (*ku)(P...), dim3 grid, dim3 block, hipStream_t s, A... args)
+{
+    hipLaunchKernelGGL((enc ? kp : ku), grid, block, 0, s, args...);
+}
+
+static dim3 lone_grid(uint32_t n) { return dim3((n + kLoneWG / 64 - 1) / (kLoneWG / 64)); }
+
+template <int SUITE, int BPL, int WG, bool CLDS>
+static void launch_gcm(const PacketLaunch &L)
+{
+    const qpp_keytab *kt = L.kt;
+    const dim3 grid(gcm_grid(L.waves, WG / 64)), block(WG);
+    const int psl = WG == 1024 && kt->n_suite[SUITE] == 1 ? pool_acquire(kt) : -1;
+    uint32_t *pl = psl >= 0 ? kt->pool->d + (size_t)psl * kPoolStride : nullptr;
+    if (CLDS) g_close_lds_launches.fetch_add(1, std::memory_order_relaxed);
+    launch_dir(L.enc, k_gcm<SUITE, true, WG, BPL, CLDS>, k_gcm<SUITE, false, WG, BPL, CLDS>,
+               grid, block, L.s, kt->d_slots, kt->d_gtab, kt->cap, L.d_desc, L.n, L.d_in, L.d_out, L.d_res,
+               L.d_items, L.d_irange, pl);
+    pool_release(kt, psl, L.s);
+}
+
+// 1024 threads: unplanned with one key of the suite in the table, the
+// close-from-LDS form (three of its four H^4 entries would sit idle)
+template <int SUITE, int BPL>
+static void launch_gcm_shape(const PacketLaunch &L)
+{
+    if (BPL == 2 && gcm_two_wg(L.kt, SUITE, L.waves)) launch_gcm<SUITE, BPL, 512, false>(L);
+    else if (!L.planned && L.kt->n_suite[SUITE] == 1) launch_gcm<SUITE, BPL, kGcmWG, true>(L);
+    else launch_gcm<SUITE, BPL, kGcmWG, false>(L);
+}
+
+template <int SUITE>
+static int launch_gcm_suite(const PacketLaunch &L)
+{
+    if (L.lone && L.n <= lone_max(SUITE))
+        launch_dir(L.enc, k_lone_gcm<SUITE, true>, k_lone_gcm<SUITE, false>, lone_grid(L.n), dim3(kLoneWG), L.s,
+                   L.kt->d_slots, L.kt->d_gtab, L.kt->cap, L.d_desc, L.n, L.d_in, L.d_out, L.d_res, L.lst);
+    else if (L.bpl_gcm == 1) launch_gcm_shape<SUITE, 1>(L);
+    else launch_gcm_shape<SUITE, 2>(L);
+    HIPCHK(hipGetLastError());
+    return QPP_OK;
+}
+
+int qpp_internal_launch_packets(bool enc, const qpp_keytab *kt, const qpp_desc *d_desc, uint32_t n,
+                                const uint8_t *d_in, uint8_t *d_out, qpp_result *d_res, void *stream,
+                                const qpp_plan *plan, const LoneStage *stage)
 {
     if (!kt || (n && (!d_desc || !d_in || !d_out || !d_res))) return QPP_E_ARG;
     if (n == 0) return QPP_OK;
@@ -3217,100 +3202,49 @@ static int launch_packets(bool enc, const qpp_keytab *kt, const qpp_desc *d_desc
     // the no-key bucket has its own kernel)
     uint32_t mask = keytab_suite_mask(kt);
     if (!mask && !plan) mask = 1u;
+    PacketLaunch L{enc, kt, d_desc, n, d_in, d_out, d_res, s, plan != nullptr};
+    L.d_items = plan ? plan->d_items : nullptr;
+    L.d_irange = plan ? plan->d_irange : nullptr;
     // planned: each suite's launch covers at most every wave item of the batch
-    const uint32_t *d_items = plan ? plan->d_items : nullptr, *d_irange = plan ? plan->d_irange : nullptr;
-    const uint32_t waves = plan ? qpp_internal_plan_max_items(n, kt->cap) : (n + 15) / 16;
-    const int bpl_gcm = gcm_bpl_choice();
+    L.waves = plan ? qpp_internal_plan_max_items(n, kt->cap) : (n + 15) / 16;
+    L.bpl_gcm = gcm_bpl_choice();
     // up to a few thousand packets (the object API's one, small flushes):
     // one wave per packet (k_lone_*), see lone_max
-    const bool lone = !plan && lone_choice();
-    const dim3 lgrid((n + kLoneWG / 64 - 1) / (kLoneWG / 64)), lblock(kLoneWG);
-    const LoneStage lst = stage ? *stage : LoneStage{nullptr, nullptr, 0u};
-#define QPP_LAUNCH_GCM_W(SUITE, BPLV, WGV, CLDSV)                                              \
-    do {                                                                                       \
-        const dim3 grid(gcm_grid(waves, WGV / 64)), block(WGV);                                 \
-        const int psl = WGV == 1024 && kt->n_suite[SUITE] == 1 ? pool_acquire(kt) : -1;        \
-        uint32_t *pl = psl >= 0 ? kt->pool->d + (size_t)psl * kPoolStride : nullptr;          \
-        if (CLDSV) g_close_lds_launches.fetch_add(1, std::memory_order_relaxed);               \
-        if (enc)                                                                               \
-            hipLaunchKernelGGL((k_gcm<SUITE, true, WGV, BPLV, CLDSV>), grid, block, 0, s,      \
-                               kt->d_slots, kt->d_gtab, kt->cap, d_desc, n, d_in, d_out, d_res, \
-                               d_items, d_irange, pl);                                         \
-        else                                                                                   \
-            hipLaunchKernelGGL((k_gcm<SUITE, false, WGV, BPLV, CLDSV>), grid, block, 0, s,     \
-                               kt->d_slots, kt->d_gtab, kt->cap, d_desc, n, d_in, d_out, d_res, \
-                               d_items, d_irange, pl);                                         \
-        pool_release(kt, psl, s);                                                              \
-    } while (0)
-    // 1024 threads: unplanned with one key of the suite in the table, the
-    // close-from-LDS form (three of its four H^4 entries would sit idle)
-#define QPP_LAUNCH_GCM_B(SUITE, BPLV)                                                          \
-    do {                                                                                       \
-        if (BPLV == 2 && gcm_two_wg(kt, SUITE, waves)) QPP_LAUNCH_GCM_W(SUITE, BPLV, 512, false); \
-        else if (!plan && kt->n_suite[SUITE] == 1) QPP_LAUNCH_GCM_W(SUITE, BPLV, kGcmWG, true);  \
-        else QPP_LAUNCH_GCM_W(SUITE, BPLV, kGcmWG, false);                                      \
-    } while (0)
-#define QPP_LAUNCH_GCM(SUITE)                                                                  \
-    if (mask & (1u << SUITE)) {                                                                \
-        if (lone && n <= lone_max(SUITE)) {                                                    \
-            if (enc)                                                                           \
-                hipLaunchKernelGGL((k_lone_gcm<SUITE, true>), lgrid, lblock, 0, s, kt->d_slots, \
-                                   kt->d_gtab, kt->cap, d_desc, n, d_in, d_out, d_res, lst);   \
-            else                                                                               \
-                hipLaunchKernelGGL((k_lone_gcm<SUITE, false>), lgrid, lblock, 0, s, kt->d_slots, \
-                                   kt->d_gtab, kt->cap, d_desc, n, d_in, d_out, d_res, lst);   \
-        } else if (bpl_gcm == 1) {                                                             \
-            QPP_LAUNCH_GCM_B(SUITE, 1);                                                         \
-        } else {                                                                               \
-            QPP_LAUNCH_GCM_B(SUITE, 2);                                                         \
-        }                                                                                      \
-        HIPCHK(hipGetLastError());                                                             \
-    }
-    QPP_LAUNCH_GCM(QPP_AES_128_GCM)
-    QPP_LAUNCH_GCM(QPP_AES_256_GCM)
-    if ((mask & (1u << QPP_CHACHA20_POLY1305)) && lone && n <= lone_max(QPP_CHACHA20_POLY1305)) {
-        if (enc)
-            hipLaunchKernelGGL((k_lone_chacha<true>), lgrid, lblock, 0, s, kt->d_slots, kt->cap, d_desc, n, d_in,
-                               d_out, d_res, lst);
-        else
-            hipLaunchKernelGGL((k_lone_chacha<false>), lgrid, lblock, 0, s, kt->d_slots, kt->cap, d_desc, n, d_in,
-                               d_out, d_res, lst);
-        HIPCHK(hipGetLastError());
-    } else if (mask & (1u << QPP_CHACHA20_POLY1305)) {
-        const uint32_t cgrid = (waves + kChachaWG / 64 - 1) / (kChachaWG / 64);
-        const dim3 grid(cgrid ? cgrid : 1u), block(kChachaWG);
-        if (chacha_prio(waves)) {
-            if (enc)
-                hipLaunchKernelGGL((k_chacha<true, kChachaWG, true>), grid, block, 0, s, kt->d_slots, kt->cap,
-                                   d_desc, n, d_in, d_out, d_res, d_items, d_irange);
-            else
-                hipLaunchKernelGGL((k_chacha<false, kChachaWG, true>), grid, block, 0, s, kt->d_slots, kt->cap,
-                                   d_desc, n, d_in, d_out, d_res, d_items, d_irange);
-        } else if (enc) {
-            hipLaunchKernelGGL((k_chacha<true, kChachaWG, false>), grid, block, 0, s, kt->d_slots, kt->cap,
-                               d_desc, n, d_in, d_out, d_res, d_items, d_irange);
+    L.lone = !plan && lone_choice();
+    L.lst = stage ? *stage : LoneStage{nullptr, nullptr, 0u};
+    if (mask & (1u << QPP_AES_128_GCM))
+        if (int rc = launch_gcm_suite<QPP_AES_128_GCM>(L)) return rc;
+    if (mask & (1u << QPP_AES_256_GCM))
+        if (int rc = launch_gcm_suite<QPP_AES_256_GCM>(L)) return rc;
+    if (mask & (1u << QPP_CHACHA20_POLY1305)) {
+        if (L.lone && n <= lone_max(QPP_CHACHA20_POLY1305)) {
+            launch_dir(enc, k_lone_chacha<true>, k_lone_chacha<false>, lone_grid(n), dim3(kLoneWG), s, kt->d_slots,
+                       kt->cap, d_desc, n, d_in, d_out, d_res, L.lst);
         } else {
-            hipLaunchKernelGGL((k_chacha<false, kChachaWG, false>), grid, block, 0, s, kt->d_slots, kt->cap,
-                               d_desc, n, d_in, d_out, d_res, d_items, d_irange);
+            const uint32_t cgrid = (L.waves + kChachaWG / 64 - 1) / (kChachaWG / 64);
+            const dim3 grid(cgrid ? cgrid : 1u), block(kChachaWG);
+            if (chacha_prio(L.waves))
+                launch_dir(enc, k_chacha<true, kChachaWG, true>, k_chacha<false, kChachaWG, true>, grid, block, s,
+                           kt->d_slots, kt->cap, d_desc, n, d_in, d_out, d_res, L.d_items, L.d_irange);
+            else
+                launch_dir(enc, k_chacha<true, kChachaWG, false>, k_chacha<false, kChachaWG, false>, grid, block, s,
+                           kt->d_slots, kt->cap, d_desc, n, d_in, d_out, d_res, L.d_items, L.d_irange);
         }
         HIPCHK(hipGetLastError());
     }
-#undef QPP_LAUNCH_GCM
-#undef QPP_LAUNCH_GCM_B
-#undef QPP_LAUNCH_GCM_W
     return QPP_OK;
 }
 
 int qpp_protect(const qpp_keytab *kt, const qpp_desc *d_desc, uint32_t n, const uint8_t *d_in,
                 uint8_t *d_out, qpp_result *d_res, void *stream)
 {
-    return launch_packets(true, kt, d_desc, n, d_in, d_out, d_res, stream);
+    return qpp_internal_launch_packets(true, kt, d_desc, n, d_in, d_out, d_res, stream);
 }
 
 int qpp_unprotect(const qpp_keytab *kt, const qpp_desc *d_desc, uint32_t n,
                   const uint8_t *d_in, uint8_t *d_out, qpp_result *d_res, void *stream)
 {
-    return launch_packets(false, kt, d_desc, n, d_in, d_out, d_res, stream);
+    return qpp_internal_launch_packets(false, kt, d_desc, n, d_in, d_out, d_res, stream);
 }
 
 int qpp_plan_build(qpp_plan *p, const qpp_keytab *kt, const qpp_desc *d_desc, uint32_t n,
@@ -3329,7 +3263,7 @@ static int launch_planned(bool enc, const qpp_keytab *kt, const qpp_plan *p, con
     hipStream_t s = (hipStream_t)stream;
     int rc = qpp_internal_plan_gather(p, d_desc, n, s);
     if (rc == QPP_OK)
-        rc = launch_packets(enc, kt, p->d_sorted, n, d_in, d_out, d_res, stream, p);
+        rc = qpp_internal_launch_packets(enc, kt, p->d_sorted, n, d_in, d_out, d_res, stream, p);
     if (rc == QPP_OK) rc = qpp_internal_plan_nokey(p, d_res, s);
     return rc;
 }
@@ -3359,334 +3293,8 @@ int qpp_hp_mask(const qpp_keytab *kt, const uint32_t *d_slots, const uint8_t *d_
     return QPP_OK;
 }
 
-// ------------------------------------------------------------- sessions --
-
-static void session_free_buffers(qpp_session *s)
-{
-    if (s->h_in) (void)hipHostFree(s->h_in);
-    if (s->h_out) (void)hipHostFree(s->h_out);
-    if (s->h_misc) (void)hipHostFree(s->h_misc);
-    if (s->d_in) (void)hipFree(s->d_in);
-    if (s->d_out) (void)hipFree(s->d_out);
-    if (s->d_misc) (void)hipFree(s->d_misc);
-    s->h_in = s->h_out = s->h_misc = s->d_in = s->d_out = s->d_misc = NULL;
-    s->hd_in = s->hd_out = s->hd_misc = NULL;
-}
-
-static size_t misc_bytes_for(uint32_t max_packets)
-{
-    // descriptors + results + slot ids + samples + masks
-    return (size_t)max_packets * (sizeof(qpp_desc) + sizeof(qpp_result) + 4 + 16 + 16) + 256;
-}
-
-static int session_reserve(qpp_session *s, size_t bytes, uint32_t packets)
-{
-    if (bytes <= s->max_bytes && packets <= s->max_packets && s->h_in) return QPP_OK;
-    size_t nb = bytes > s->max_bytes ? bytes : s->max_bytes;
-    uint32_t np = packets > s->max_packets ? packets : s->max_packets;
-    if (nb < 4096) nb = 4096;
-    if (np < 64) np = 64;
-    session_free_buffers(s);
-    s->max_bytes = nb;
-    s->max_packets = np;
-    s->misc_bytes = misc_bytes_for(np);
-    if (hipHostMalloc(&s->h_in, nb, hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc(&s->h_out, nb, hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc(&s->h_misc, s->misc_bytes, hipHostMallocDefault) != hipSuccess ||
-        hipMalloc(&s->d_in, nb) != hipSuccess || hipMalloc(&s->d_out, nb) != hipSuccess ||
-        hipMalloc(&s->d_misc, s->misc_bytes) != hipSuccess ||
-        hipHostGetDevicePointer((void **)&s->hd_in, s->h_in, 0) != hipSuccess ||
-        hipHostGetDevicePointer((void **)&s->hd_out, s->h_out, 0) != hipSuccess ||
-        hipHostGetDevicePointer((void **)&s->hd_misc, s->h_misc, 0) != hipSuccess) {
-        (void)hipGetLastError();
-        session_free_buffers(s);
-        s->max_bytes = 0;
-        s->max_packets = 0;
-        return QPP_E_NOMEM;
-    }
-    return QPP_OK;
-}
-
-int qpp_session_create(size_t max_bytes, uint32_t max_packets, qpp_session **out)
-{
-    if (!out) return QPP_E_ARG;
-    *out = NULL;
-    int rc = qpp_device_check();
-    if (rc != QPP_OK) return rc;
-    qpp_session *s = (qpp_session *)calloc(1, sizeof(qpp_session));
-    if (!s) return QPP_E_NOMEM;
-    (void)hipGetDevice(&s->device);
-    if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) {
-        free(s);
-        return QPP_E_HIP;
-    }
-    bool ok = hipStreamCreateWithFlags(&s->s_in, hipStreamNonBlocking) == hipSuccess &&
-              hipStreamCreateWithFlags(&s->s_out, hipStreamNonBlocking) == hipSuccess;
-    for (int c = 0; ok && c < kPipeMaxChunks; ++c)
-        ok = hipEventCreateWithFlags(&s->ev_in[c], hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&s->ev_k[c], hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&s->ev_out[c], hipEventDisableTiming) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        qpp_session_destroy(s);
-        return QPP_E_HIP;
-    }
-    rc = session_reserve(s, max_bytes, max_packets);
-    if (rc != QPP_OK) {
-        qpp_session_destroy(s);
-        return rc;
-    }
-    *out = s;
-    return QPP_OK;
-}
-
-void qpp_session_destroy(qpp_session *s)
-{
-    if (!s) return;
-    if (s->stream) (void)hipStreamSynchronize(s->stream);
-    if (s->s_in) (void)hipStreamSynchronize(s->s_in);
-    if (s->s_out) (void)hipStreamSynchronize(s->s_out);
-    session_free_buffers(s);
-    if (s->h_scratch) (void)hipHostFree(s->h_scratch);
-    if (s->d_scratch) (void)hipFree(s->d_scratch);
-    qpp_plan_destroy(s->plan);
-    for (int c = 0; c < kPipeMaxChunks; ++c) {
-        if (s->ev_in[c]) (void)hipEventDestroy(s->ev_in[c]);
-        if (s->ev_k[c]) (void)hipEventDestroy(s->ev_k[c]);
-        if (s->ev_out[c]) (void)hipEventDestroy(s->ev_out[c]);
-        for (int k = 0; k < 6; ++k)
-            if (s->tev[k][c]) (void)hipEventDestroy(s->tev[k][c]);
-    }
-    if (s->s_in) (void)hipStreamDestroy(s->s_in);
-    if (s->s_out) (void)hipStreamDestroy(s->s_out);
-    if (s->stream) (void)hipStreamDestroy(s->stream);
-    free(s);
-}
-
-void *qpp_session_stream(qpp_session *s) { return s ? (void *)s->stream : NULL; }
-
-// Large host batches: chunk c of the packets (in descriptor order) is copied
-// into pinned staging by the host and sent H2D on s_in, processed on the
-// kernel stream once its input event fires, and returned D2H on s_out once its
-// kernel event fires; the host copies chunk c out while later chunks are still
-// in flight.  The host memcpys, both PCIe directions and the kernels of
-// different chunks overlap.  Requires out_off non-decreasing in descriptor
-// order: chunk c's D2H then covers [out_off of its first packet, out_off of
-// the next chunk's first packet) -- chunk 0 from 0, the last chunk to out_len
-// -- so the chunks tile the output, and bytes a packet writes past its tile
-// are copied by a later chunk's D2H, which runs after this chunk's kernel.
-// Each chunk's H2D covers the input extent of its own packets (over-copying
-// bytes of a neighbour is harmless: same host bytes).
-// Host copies between caller memory and pinned staging: one thread streams
-// ~10 GB/s, well under the PCIe rate, so large copies are split over a
-// process-wide pool of copy threads (started on first use, never torn down:
-// its threads sleep on a condition variable between copies).  Round 5: the
-// pool replaces a std::thread per part and copy (up to 8 x 64 thread starts
-// per 1 Mi-packet call), and a chunk's copy-out runs on it while the calling
-// thread stages the next chunks.
-// Host copies between caller memory and pinned staging with non-temporal
-// stores: a plain memcpy below glibc's non-temporal threshold reads each
-// destination line before writing it (write-allocate), so a copy moves three
-// times its size through host memory instead of two.  (memcpy without AVX2.)
-static bool copy_nt_choice()
-{
-    static const bool b = __builtin_cpu_supports("avx2");
-    return b;
-}
-
-__attribute__((target("avx2"))) static void copy_nt_avx2(uint8_t *dst, const uint8_t *src, size_t n)
-{
-    size_t head = (size_t)((32u - ((uintptr_t)dst & 31u)) & 31u);
-    if (head > n) head = n;
-    memcpy(dst, src, head);
-    dst += head;
-    src += head;
-    n -= head;
-    size_t i = 0;
-    for (; i + 128 <= n; i += 128) {
-        const __m256i a = _mm256_loadu_si256((const __m256i *)(src + i));
-        const __m256i b = _mm256_loadu_si256((const __m256i *)(src + i + 32));
-        const __m256i c = _mm256_loadu_si256((const __m256i *)(src + i + 64));
-        const __m256i d = _mm256_loadu_si256((const __m256i *)(src + i + 96));
-        _mm256_stream_si256((__m256i *)(dst + i), a);
-        _mm256_stream_si256((__m256i *)(dst + i + 32), b);
-        _mm256_stream_si256((__m256i *)(dst + i + 64), c);
-        _mm256_stream_si256((__m256i *)(dst + i + 96), d);
-    }
-    memcpy(dst + i, src + i, n - i);
-    _mm_sfence();  // the streamed lines are visible before the copy is reported done
-}
-
-static void copy_bytes(uint8_t *dst, const uint8_t *src, size_t n)
-{
-    if (n >= ((size_t)1 << 16) && copy_nt_choice()) copy_nt_avx2(dst, src, n);
-    else memcpy(dst, src, n);
-}
-
-struct CopyGroup {
-    std::mutex mu;
-    std::condition_variable cv;
-    int pending = 0;
-    std::atomic<uint64_t> busy_ns{0};  // summed duration of the pool's tasks (qpp_trace)
-    void wait()
-    {
-        std::unique_lock<std::mutex> l(mu);
-        cv.wait(l, [&] { return pending == 0; });
-    }
-};
-
-constexpr int kCopyThreads = 6;  // 2, 3, 4, 8 and 12 measured within the spread of 6
-class CopyPool {
-  public:
-    static CopyPool &get()
-    {
-        // never destroyed (no join at exit); a forked child, which inherits
-        // the pointer but not the threads, starts a pool of its own
-        static std::once_flag once;
-        std::call_once(once, [] { pthread_atfork(nullptr, nullptr, [] { g_pool.store(nullptr); }); });
-        CopyPool *p = g_pool.load();
-        if (!p) {
-            std::lock_guard<std::mutex> l(g_pool_mu);
-            p = g_pool.load();
-            if (!p) {
-                p = new CopyPool();
-                g_pool.store(p);
-            }
-        }
-        return *p;
-    }
-    int threads() const { return n_; }
-    void submit(uint8_t *dst, const uint8_t *src, size_t len, CopyGroup *g)
-    {
-        {
-            std::lock_guard<std::mutex> l(g->mu);
-            ++g->pending;
-        }
-        {
-            std::lock_guard<std::mutex> l(mu_);
-            q_.push_back(Task{dst, src, len, g});
-        }
-        cv_.notify_one();
-    }
-
-  private:
-    struct Task {
-        uint8_t *dst;
-        const uint8_t *src;
-        size_t len;
-        CopyGroup *g;
-    };
-    CopyPool()
-    {
-        // (round 5 also pinned the threads to the CPUs of the device's NUMA
-        // node: 13.0-16.6 against 11.5-17.7 GiB/s unpinned on one two-socket
-        // box, interleaved -- no difference through the run-to-run spread,
-        // profiles/r5e_host_path/host_path_studies.txt; removed)
-        for (int i = 0; i < n_; ++i) std::thread([this] { run(); }).detach();
-    }
-    void run()
-    {
-        for (;;) {
-            Task t;
-            {
-                std::unique_lock<std::mutex> l(mu_);
-                cv_.wait(l, [&] { return !q_.empty(); });
-                t = q_.front();
-                q_.pop_front();
-            }
-            const auto t0 = std::chrono::steady_clock::now();
-            copy_bytes(t.dst, t.src, t.len);
-            t.g->busy_ns.fetch_add((uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(
-                                       std::chrono::steady_clock::now() - t0).count(),
-                                   std::memory_order_relaxed);
-            {
-                // notify while holding the group's lock: the waiter cannot see
-                // pending == 0 (and destroy the group, which lives on its
-                // stack) until this worker has released the lock, after which
-                // it never touches the group again
-                std::lock_guard<std::mutex> l(t.g->mu);
-                if (--t.g->pending == 0) t.g->cv.notify_all();
-            }
-        }
-    }
-    const int n_ = kCopyThreads;
-    std::mutex mu_;
-    std::condition_variable cv_;
-    std::deque<Task> q_;
-    static std::atomic<CopyPool *> g_pool;
-    static std::mutex g_pool_mu;
-};
-std::atomic<CopyPool *> CopyPool::g_pool{nullptr};
-std::mutex CopyPool::g_pool_mu;
-
-// dst <- src over the pool's threads in parts of >= 4 MiB; with g, return at
-// once (g->wait() before the bytes are used), else when the copy is done.
-static void par_memcpy(uint8_t *dst, const uint8_t *src, size_t bytes, CopyGroup *g = nullptr)
-{
-    constexpr size_t kPart = (size_t)4 << 20;
-    if (bytes < 2 * kPart) {
-        const auto t0 = std::chrono::steady_clock::now();
-        copy_bytes(dst, src, bytes);
-        if (g)
-            g->busy_ns.fetch_add((uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(
-                                     std::chrono::steady_clock::now() - t0).count(),
-                                 std::memory_order_relaxed);
-        return;
-    }
-    CopyPool &pool = CopyPool::get();
-    size_t parts = bytes / kPart;
-    if (parts > (size_t)pool.threads()) parts = (size_t)pool.threads();
-    const size_t step = (bytes / parts + 63) & ~(size_t)63;
-    CopyGroup local;
-    CopyGroup *grp = g ? g : &local;
-    for (size_t lo = g ? 0 : step; lo < bytes; lo += step)
-        pool.submit(dst + lo, src + lo, lo + step < bytes ? step : bytes - lo, grp);
-    if (!g) {
-        copy_bytes(dst, src, step < bytes ? step : bytes);  // the caller's own part
-        local.wait();
-    }
-}
-
-// Descriptor extents against the caller's buffer sizes (quic_pp.h, Buffers):
-// a descriptor that does not fit is flagged so the kernel reports
-// QPP_S_LENGTH for it without touching memory.  Protect reads header +
-// payload and writes header + ciphertext + tag; unprotect reads and writes
-// at most the packet's length.
-static void reject_out_of_bounds(bool enc, qpp_desc *d, uint32_t n, size_t in_len, size_t out_len)
-{
-    for (uint32_t i = 0; i < n; ++i) {
-        const uint64_t rd = enc ? (uint64_t)d[i].hdr_len + d[i].len : (uint64_t)d[i].len;
-        const uint64_t wr = enc ? rd + QPP_TAG_LEN : rd;
-        const bool ok = d[i].in_off <= in_len && rd <= in_len - d[i].in_off && d[i].out_off <= out_len &&
-                        wr <= out_len - d[i].out_off;
-        d[i].flags = ok ? (uint16_t)(d[i].flags & ~kFlagReject) : (uint16_t)(d[i].flags | kFlagReject);
-    }
-}
-
-// One launch over n device descriptors of the session: bucketed by (suite,
-// slot) through the session's plan when the batch is large enough.
-static int session_launch(bool enc, qpp_session *s, const qpp_keytab *kt, const qpp_desc *dd,
-                          uint32_t n, qpp_result *dr)
-{
-    if (n < kSessionPlanMin) return launch_packets(enc, kt, dd, n, s->d_in, s->d_out, dr, s->stream);
-    if (s->plan && s->plan->cap < n) {
-        HIPCHK(hipStreamSynchronize(s->stream));  // the old plan may still be in use
-        qpp_plan_destroy(s->plan);
-        s->plan = NULL;
-    }
-    if (!s->plan) {
-        const int rc = qpp_plan_create(n > s->max_packets ? n : s->max_packets, &s->plan);
-        if (rc != QPP_OK) return rc;
-    }
-    int rc = qpp_plan_build(s->plan, kt, dd, n, s->stream);
-    if (rc == QPP_OK) rc = launch_planned(enc, kt, s->plan, dd, n, s->d_in, s->d_out, dr, s->stream);
-    return rc;
-}
-
-// D2H of a session: up to two device ranges into pinned host memory (device
-// views), by k_xfer.
-static int launch_xfer(uint8_t *d0, const uint8_t *s0, size_t n0, uint8_t *d1, const uint8_t *s1, size_t n1,
-                       hipStream_t st)
+int qpp_internal_launch_xfer(uint8_t *d0, const uint8_t *s0, size_t n0, uint8_t *d1, const uint8_t *s1, size_t n1,
+                             hipStream_t st)
 {
     if (!n0 && !n1) return QPP_OK;
     const size_t units = (std::max(n0, n1) + 15) / 16;
@@ -3699,600 +3307,3 @@ static int launch_xfer(uint8_t *d0, const uint8_t *s0, size_t n0, uint8_t *d1, c
     HIPCHK(hipGetLastError());
     return QPP_OK;
 }
-
-// Chunk c of the batch: its descriptors are copied into pinned staging and
-// bounds-checked by the host, its input extent is copied into pinned staging
-// by the copy pool, and both go H2D on s_in (the copy engines); the chunk's
-// kernels run on the kernel stream once that lands; its output tile and
-// results go D2H on s_out (a blit kernel, the runtime's choice, which runs
-// beside the packet kernels: profiles/r5g_d2h_engines.txt), and the pool
-// copies them out while later chunks are in flight.  So host copies, both
-// PCIe directions and the kernels of different chunks overlap, and no work
-// on the whole batch precedes the first chunk's copies.  (Round 5 also built
-// DMA straight from / to caller memory pinned by hipHostRegister: correct,
-// but 9.6-10.7 GiB/s against 17-19 GiB/s for this staged pipeline on the
-// same boxes whatever the flags and D2H form, so it was removed;
-// profiles/r5e_host_path/.)
-static int session_run_pipelined(bool enc, qpp_session *s, const qpp_keytab *kt,
-                                 const qpp_desc *desc, uint32_t n, const uint8_t *in,
-                                 size_t in_len, uint8_t *out, size_t out_len, qpp_result *res,
-                                 int chunks)
-{
-    qpp_desc *hd = (qpp_desc *)s->h_misc;
-    qpp_result *hr = (qpp_result *)(s->h_misc + (size_t)s->max_packets * sizeof(qpp_desc));
-    qpp_desc *dd = (qpp_desc *)s->d_misc;
-    qpp_result *dr = (qpp_result *)(s->d_misc + (size_t)s->max_packets * sizeof(qpp_desc));
-    qpp_result *hrd = (qpp_result *)(s->hd_misc + (size_t)s->max_packets * sizeof(qpp_desc));  // hr's device view
-    const bool tr = s->trace;
-    const auto clk = [] { return std::chrono::duration<double, std::milli>(
-                              std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t_start = clk();
-    double t_copy_in = 0.0;
-    double in_bytes = 0.0, out_bytes = 0.0;
-    // the caller may have assembled its input / wants its output in the
-    // session's own staging (qpp_session_stage): no host copy then
-    const bool in_direct = in == s->h_in, out_direct = out == s->h_out;
-    HIPCHK(hipMemsetAsync(s->d_out, 0, out_len, s->stream));
-    size_t olo[kPipeMaxChunks + 1];
-    uint32_t first[kPipeMaxChunks + 1];
-    // chunk weights in quarters of a regular chunk: 1, 1, 2 at the start and
-    // 2, 1, 1 at the end when there are enough regular chunks to taper
-    const int regular = chunks;
-    const bool taper = regular >= 8;
-    if (taper) chunks = regular + 2 * kPipeTaper;
-    auto weight = [&](int c) -> uint64_t {
-        if (!taper) return 4;
-        if (c < 3) return c < 2 ? 1 : 2;
-        if (c >= chunks - 3) return c >= chunks - 2 ? 1 : 2;
-        return 4;
-    };
-    const uint64_t wsum = 4ull * (uint64_t)regular;
-    uint64_t wacc = 0;
-    for (int c = 0; c <= chunks; ++c) {
-        first[c] = (uint32_t)((uint64_t)n * wacc / wsum);
-        if (c < chunks) wacc += weight(c);
-        olo[c] = c == 0 ? 0 : c == chunks ? out_len : (size_t)desc[first[c]].out_off;
-        if (olo[c] > out_len) olo[c] = out_len;
-    }
-    // a chunk handed back to the caller: its output tile and results, copied
-    // out by the pool while this thread goes on staging later chunks
-    CopyGroup outg;
-    struct WaitAll {
-        CopyGroup &g;
-        ~WaitAll() { g.wait(); }  // every return path: no pool copy outlives the call
-    } wait_all{outg};
-    auto hand_back = [&](int d) {
-        if (olo[d + 1] > olo[d] && !out_direct)
-            par_memcpy(out + olo[d], s->h_out + olo[d], olo[d + 1] - olo[d], &outg);
-        memcpy(res + first[d], hr + first[d], (size_t)(first[d + 1] - first[d]) * sizeof(qpp_result));
-    };
-    int rc = QPP_OK;
-    int next_out = 0;
-    for (int c = 0; c < chunks; ++c) {
-        const uint32_t a = first[c], b = first[c + 1];
-        hipStream_t sin = s->s_in;
-        memcpy(hd + a, desc + a, (size_t)(b - a) * sizeof(qpp_desc));
-        reject_out_of_bounds(enc, hd + a, b - a, in_len, out_len);
-        if (tr) HIPCHK(hipEventRecord(s->tev[0][c], sin));
-        if (b > a)
-            HIPCHK(hipMemcpyAsync(dd + a, hd + a, (size_t)(b - a) * sizeof(qpp_desc), hipMemcpyHostToDevice,
-                                  sin));
-        size_t lo = SIZE_MAX, hi = 0;
-        for (uint32_t i = a; i < b; ++i) {
-            if (hd[i].flags & kFlagReject) continue;
-            const size_t o = (size_t)desc[i].in_off;
-            const size_t e = o + (size_t)desc[i].hdr_len + desc[i].len + 16;
-            if (o < lo) lo = o;
-            if (e > hi) hi = e;
-        }
-        if (hi > in_len) hi = in_len;
-        if (lo < hi) {
-            if (!in_direct) {
-                const double t0 = tr ? clk() : 0.0;
-                par_memcpy(s->h_in + lo, in + lo, hi - lo);
-                if (tr) t_copy_in += clk() - t0;
-            }
-            HIPCHK(hipMemcpyAsync(s->d_in + lo, s->h_in + lo, hi - lo, hipMemcpyHostToDevice, sin));
-            in_bytes += (double)(hi - lo);
-        }
-        in_bytes += (double)(b - a) * sizeof(qpp_desc);
-        HIPCHK(hipEventRecord(s->ev_in[c], sin));
-        if (tr) HIPCHK(hipEventRecord(s->tev[1][c], sin));
-        HIPCHK(hipStreamWaitEvent(s->stream, s->ev_in[c], 0));
-        if (tr) HIPCHK(hipEventRecord(s->tev[2][c], s->stream));
-        if (b > a) {
-            rc = session_launch(enc, s, kt, dd + a, b - a, dr + a);
-            if (rc != QPP_OK) break;
-        }
-        HIPCHK(hipEventRecord(s->ev_k[c], s->stream));
-        if (tr) HIPCHK(hipEventRecord(s->tev[3][c], s->stream));
-        HIPCHK(hipStreamWaitEvent(s->s_out, s->ev_k[c], 0));
-        if (tr) HIPCHK(hipEventRecord(s->tev[4][c], s->s_out));
-        out_bytes += (double)(olo[c + 1] - olo[c]) + (double)(b - a) * sizeof(qpp_result);
-        {
-            const size_t tl = olo[c + 1] > olo[c] ? olo[c + 1] - olo[c] : 0;
-            const size_t rl = (size_t)(b - a) * sizeof(qpp_result);
-            rc = launch_xfer(s->hd_out + olo[c], s->d_out + olo[c], tl, (uint8_t *)(hrd + a),
-                             (const uint8_t *)(dr + a), rl, s->s_out);
-            if (rc != QPP_OK) break;
-        }
-        HIPCHK(hipEventRecord(s->ev_out[c], s->s_out));
-        if (tr) HIPCHK(hipEventRecord(s->tev[5][c], s->s_out));
-        // hand back chunks whose D2H has already landed while later ones fly
-        while (next_out < c) {
-            if (hipEventQuery(s->ev_out[next_out]) != hipSuccess) {
-                (void)hipGetLastError();  // hipErrorNotReady must not reach a later HIPCHK
-                break;
-            }
-            hand_back(next_out++);
-        }
-    }
-    if (rc != QPP_OK) return rc;
-    const double t_sub = clk();
-    for (int c = next_out; c < chunks; ++c) {
-        HIPCHK(hipEventSynchronize(s->ev_out[c]));
-        hand_back(c);
-    }
-    HIPCHK(hipStreamSynchronize(s->s_out));
-    outg.wait();
-    const double t_end = clk();
-    if (tr) {
-        qpp_trace &T = s->last;
-        T = qpp_trace{};
-        T.pipelined = 1;
-        T.chunks = (uint32_t)chunks;
-        T.total_ms = t_end - t_start;
-        T.submit_ms = t_sub - t_start;
-        T.copy_in_ms = t_copy_in;
-        T.copy_out_ms = (double)outg.busy_ns.load() * 1e-6;
-        T.wait_ms = t_end - t_sub;
-        T.in_bytes = in_bytes;
-        T.out_bytes = out_bytes;
-        float ms = 0.f;
-        for (int c = 0; c < chunks; ++c) {
-            HIPCHK(hipEventElapsedTime(&ms, s->tev[0][c], s->tev[1][c]));
-            T.h2d_ms += ms;
-            HIPCHK(hipEventElapsedTime(&ms, s->tev[2][c], s->tev[3][c]));
-            T.kernel_ms += ms;
-            HIPCHK(hipEventElapsedTime(&ms, s->tev[4][c], s->tev[5][c]));
-            T.d2h_ms += ms;
-        }
-        HIPCHK(hipEventElapsedTime(&ms, s->tev[0][0], s->tev[5][chunks - 1]));
-        T.gpu_span_ms = ms;
-    }
-    return QPP_OK;
-}
-
-// On a failure, drain the session's streams before returning, so no copy into
-// its staging is still in flight when the staging is reused or freed.
-static int session_drain_on_error(qpp_session *s, int rc)
-{
-    if (rc != QPP_OK && s) {
-        if (s->s_in) (void)hipStreamSynchronize(s->s_in);
-        (void)hipStreamSynchronize(s->stream);
-        if (s->s_out) (void)hipStreamSynchronize(s->s_out);
-        (void)hipGetLastError();
-    }
-    return rc;
-}
-
-constexpr uint32_t kSmallPackets = 64;
-constexpr size_t kSmallBytes = (size_t)256 << 10;
-static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-static int session_run(bool enc, qpp_session *s, const qpp_keytab *kt, const qpp_desc *desc,
-                       uint32_t n, const uint8_t *in, size_t in_len, uint8_t *out, size_t out_len,
-                       qpp_result *res)
-{
-    if (!s || !kt || (n && (!desc || !res))) return QPP_E_ARG;
-    if (n == 0) return QPP_OK;
-    size_t need = in_len > out_len ? in_len : out_len;
-    int rc = session_reserve(s, need, n);
-    if (rc != QPP_OK) return rc;
-    size_t want = out_len / kPipeChunkBytes;
-    int chunks = want > (size_t)kPipeRegular ? kPipeRegular : (int)want;
-    if (chunks > (int)n) chunks = (int)n;
-    // QPP_SESSION_SERIAL=1 (an A/B and test switch, read at every call): the serial path
-    if (chunks >= 2 && qpp_env_long("QPP_SESSION_SERIAL", 0) != 1) {
-        bool mono = true;
-        for (uint32_t i = 1; i < n && mono; ++i) mono = desc[i].out_off >= desc[i - 1].out_off;
-        if (mono)
-            return session_run_pipelined(enc, s, kt, desc, n, in, in_len, out, out_len, res,
-                                         chunks);
-    }
-    // Small batches (the per-call object API: one packet per call): one H2D
-    // copy of [descriptors | input | zeroed output] and one D2H copy of
-    // [output | results] through the session's input staging, instead of
-    // four copies and a device memset.
-    const size_t sd = al256((size_t)n * sizeof(qpp_desc)), si = al256(in_len), so = al256(out_len);
-    const size_t small = sd + si + so + (size_t)n * sizeof(qpp_result);
-    if (n <= kSmallPackets && small <= kSmallBytes && in != s->h_in && out != s->h_out) {
-        rc = session_reserve(s, small > need ? small : need, n);
-        if (rc != QPP_OK) return rc;
-        uint8_t *h = s->h_in, *d = s->d_in;
-        memcpy(h, desc, (size_t)n * sizeof(qpp_desc));
-        reject_out_of_bounds(enc, (qpp_desc *)h, n, in_len, out_len);
-        if (in_len) memcpy(h + sd, in, in_len);
-        memset(h + sd + si, 0, out_len);  // bytes the kernel does not write come back as zeros
-        if (n <= std::min(lone_max(QPP_AES_128_GCM), lone_max(QPP_CHACHA20_POLY1305)) && lone_choice() &&
-            zero_copy_choice()) {
-            // one wave per packet; the output and results are written by
-            // the kernel straight into the pinned staging (PCIe writes post;
-            // reads there would put a bus round trip on each of the kernel's
-            // dependent loads).  Descriptors and input: copied by the kernel
-            // itself in one round trip when the call fits one workgroup,
-            // else by one copy
-            uint8_t *dh = s->hd_in;
-            LoneStage st{dh, d, 0u};
-            if (n <= (uint32_t)(kLoneWG / 64) && sd + si <= kLoneStageMax && lone_stage_choice())
-                st.bytes = (uint32_t)(sd + si);  // 256-byte multiples
-            else
-                HIPCHK(hipMemcpyAsync(d, h, sd + si, hipMemcpyHostToDevice, s->stream));
-            rc = launch_packets(enc, kt, (const qpp_desc *)d, n, d + sd, dh + sd + si,
-                                (qpp_result *)(dh + sd + si + so), s->stream, nullptr, &st);
-            if (rc != QPP_OK) return rc;
-            HIPCHK(hipStreamSynchronize(s->stream));
-            if (out_len) memcpy(out, h + sd + si, out_len);
-            memcpy(res, h + sd + si + so, (size_t)n * sizeof(qpp_result));
-            return QPP_OK;
-        }
-        HIPCHK(hipMemcpyAsync(d, h, sd + si + out_len, hipMemcpyHostToDevice, s->stream));
-        rc = launch_packets(enc, kt, (const qpp_desc *)d, n, d + sd, d + sd + si,
-                            (qpp_result *)(d + sd + si + so), s->stream);
-        if (rc != QPP_OK) return rc;
-        HIPCHK(hipMemcpyAsync(h + sd + si, d + sd + si, so + (size_t)n * sizeof(qpp_result),
-                              hipMemcpyDeviceToHost, s->stream));
-        HIPCHK(hipStreamSynchronize(s->stream));
-        if (out_len) memcpy(out, h + sd + si, out_len);
-        memcpy(res, h + sd + si + so, (size_t)n * sizeof(qpp_result));
-        return QPP_OK;
-    }
-    qpp_desc *hd = (qpp_desc *)s->h_misc;
-    qpp_result *hr = (qpp_result *)(s->h_misc + (size_t)s->max_packets * sizeof(qpp_desc));
-    qpp_desc *dd = (qpp_desc *)s->d_misc;
-    qpp_result *dr = (qpp_result *)(s->d_misc + (size_t)s->max_packets * sizeof(qpp_desc));
-    memcpy(hd, desc, (size_t)n * sizeof(qpp_desc));
-    reject_out_of_bounds(enc, hd, n, in_len, out_len);
-    if (in_len && in != s->h_in) memcpy(s->h_in, in, in_len);  // staged by the caller already?
-    HIPCHK(hipMemcpyAsync(dd, hd, (size_t)n * sizeof(qpp_desc), hipMemcpyHostToDevice, s->stream));
-    if (in_len) HIPCHK(hipMemcpyAsync(s->d_in, s->h_in, in_len, hipMemcpyHostToDevice, s->stream));
-    // bytes the kernel does not write (gaps, failed packets) come back as zeros
-    if (out_len) HIPCHK(hipMemsetAsync(s->d_out, 0, out_len, s->stream));
-    rc = session_launch(enc, s, kt, dd, n, dr);
-    if (rc != QPP_OK) return rc;
-    rc = launch_xfer(s->hd_out, s->d_out, out_len, s->hd_misc + (size_t)s->max_packets * sizeof(qpp_desc),
-                     (const uint8_t *)dr, (size_t)n * sizeof(qpp_result), s->stream);
-    if (rc != QPP_OK) return rc;
-    HIPCHK(hipStreamSynchronize(s->stream));
-    if (out_len && out != s->h_out) memcpy(out, s->h_out, out_len);
-    memcpy(res, hr, (size_t)n * sizeof(qpp_result));
-    return QPP_OK;
-}
-
-int qpp_session_protect(qpp_session *s, const qpp_keytab *kt, const qpp_desc *desc, uint32_t n,
-                        const uint8_t *in, size_t in_len, uint8_t *out, size_t out_len,
-                        qpp_result *res)
-{
-    return session_drain_on_error(s, session_run(true, s, kt, desc, n, in, in_len, out, out_len, res));
-}
-
-int qpp_session_unprotect(qpp_session *s, const qpp_keytab *kt, const qpp_desc *desc,
-                          uint32_t n, const uint8_t *in, size_t in_len, uint8_t *out,
-                          size_t out_len, qpp_result *res)
-{
-    return session_drain_on_error(s, session_run(false, s, kt, desc, n, in, in_len, out, out_len, res));
-}
-
-int qpp_session_trace(qpp_session *s, int enable, qpp_trace *last)
-{
-    if (!s) return QPP_E_ARG;
-    if (last) *last = s->last;
-    if (enable > 0 && !s->tev[0][0]) {
-        for (int k = 0; k < 6; ++k)
-            for (int c = 0; c < kPipeMaxChunks; ++c)
-                if (hipEventCreate(&s->tev[k][c]) != hipSuccess) {
-                    (void)hipGetLastError();
-                    for (int k2 = 0; k2 < 6; ++k2)
-                        for (int c2 = 0; c2 < kPipeMaxChunks; ++c2) {
-                            if (s->tev[k2][c2]) (void)hipEventDestroy(s->tev[k2][c2]);
-                            s->tev[k2][c2] = nullptr;
-                        }
-                    return QPP_E_HIP;
-                }
-    }
-    if (enable >= 0) s->trace = enable > 0;
-    if (s->trace) s->last = qpp_trace{};  // a call that does not pipeline reports pipelined = 0
-    return QPP_OK;
-}
-
-int qpp_session_stage(qpp_session *s, size_t bytes, uint32_t n, uint8_t **h_in, uint8_t **h_out)
-{
-    if (!s || !h_in || !h_out) return QPP_E_ARG;
-    const int rc = session_reserve(s, bytes, n);
-    if (rc != QPP_OK) return rc;
-    *h_in = s->h_in;
-    *h_out = s->h_out;
-    return QPP_OK;
-}
-
-}  // extern "C"
-
-// The session's staging, sized as by qpp_session_stage, and `scratch` bytes of
-// pinned and device scratch beside it (qpp_internal.h).
-int qpp_internal_session_bufs(qpp_session *s, size_t bytes, uint32_t packets, size_t scratch,
-                              qpp_session_bufs *out)
-{
-    if (!s || !out) return QPP_E_ARG;
-    const int rc = session_reserve(s, bytes, packets);
-    if (rc != QPP_OK) return rc;
-    if (scratch > s->scratch_bytes) {
-        HIPCHK(hipStreamSynchronize(s->stream));
-        if (s->h_scratch) (void)hipHostFree(s->h_scratch);
-        if (s->d_scratch) (void)hipFree(s->d_scratch);
-        s->h_scratch = s->d_scratch = NULL;
-        s->scratch_bytes = 0;
-        if (hipHostMalloc(&s->h_scratch, scratch, hipHostMallocDefault) != hipSuccess ||
-            hipMalloc(&s->d_scratch, scratch) != hipSuccess) {
-            (void)hipGetLastError();
-            if (s->h_scratch) (void)hipHostFree(s->h_scratch);
-            s->h_scratch = NULL;
-            return QPP_E_NOMEM;
-        }
-        s->scratch_bytes = scratch;
-    }
-    *out = qpp_session_bufs{s->stream, s->h_in, s->h_out, s->d_in, s->d_out, s->h_scratch, s->d_scratch};
-    return QPP_OK;
-}
-
-extern "C" {
-
-int qpp_session_hp_mask(qpp_session *s, const qpp_keytab *kt, const uint32_t *slots,
-                        const uint8_t *samples, uint32_t n, uint8_t *masks)
-{
-    if (!s || !kt || (n && (!slots || !samples || !masks))) return QPP_E_ARG;
-    if (n == 0) return QPP_OK;
-    int rc = session_reserve(s, (size_t)n * 32, n);
-    if (rc != QPP_OK) return rc;
-    uint8_t *hs = s->h_in, *hm = s->h_out;
-    uint32_t *hidx = (uint32_t *)s->h_misc;
-    memcpy(hidx, slots, (size_t)n * 4);
-    memcpy(hs, samples, (size_t)n * 16);
-    if (n <= kSmallPackets && zero_copy_choice()) {
-        rc = qpp_hp_mask(kt, (const uint32_t *)s->hd_misc, s->hd_in, n, s->hd_out, s->stream);
-        if (rc != QPP_OK) return rc;
-        HIPCHK(hipStreamSynchronize(s->stream));
-        memcpy(masks, hm, (size_t)n * 16);
-        return QPP_OK;
-    }
-    HIPCHK(hipMemcpyAsync(s->d_misc, hidx, (size_t)n * 4, hipMemcpyHostToDevice, s->stream));
-    HIPCHK(hipMemcpyAsync(s->d_in, hs, (size_t)n * 16, hipMemcpyHostToDevice, s->stream));
-    rc = qpp_hp_mask(kt, (const uint32_t *)s->d_misc, s->d_in, n, s->d_out, s->stream);
-    if (rc != QPP_OK) return rc;
-    HIPCHK(hipMemcpyAsync(hm, s->d_out, (size_t)n * 16, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    memcpy(masks, hm, (size_t)n * 16);
-    return QPP_OK;
-}
-
-int qpp_session_set_keys(qpp_session *s, qpp_keytab *kt, const qpp_key_material *km, uint32_t n)
-{
-    if (!s) return QPP_E_ARG;
-    return qpp_keytab_set(kt, km, n, s->stream);
-}
-
-// ------------------------------------------------------ several devices --
-//
-// One host batch over several GPUs of the node (packets
-// are independent, so no collective): a session and a replica of the key
-// table per device; the batch is cut into contiguous descriptor ranges, one
-// per device, each range's input and output extents are staged and run by its
-// own host thread on its own device, and every result lands at its packet's
-// position in the caller's arrays.  Each range needs its own output extent,
-// so the ranges' output extents must not overlap (descriptors in output
-// order, the layout of a socket batch); otherwise the batch runs on the first
-// device alone.  Output bytes outside every packet are zeros, as for one
-// session.
-
-struct qpp_multi {
-    int n;
-    int device[kMultiMaxDevices];
-    qpp_session *s[kMultiMaxDevices];
-    qpp_keytab *kt[kMultiMaxDevices];
-};
-
-int qpp_multi_create(const int *devices, int n_devices, uint32_t key_capacity, qpp_multi **out)
-{
-    if (!out || !devices || n_devices < 1 || n_devices > kMultiMaxDevices) return QPP_E_ARG;
-    *out = NULL;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess) return QPP_E_NODEV;
-    for (int k = 0; k < n_devices; ++k)
-        if (devices[k] < 0 || devices[k] >= count) return QPP_E_ARG;
-    qpp_multi *m = (qpp_multi *)calloc(1, sizeof(qpp_multi));
-    if (!m) return QPP_E_NOMEM;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    int rc = QPP_OK;
-    for (int k = 0; k < n_devices && rc == QPP_OK; ++k) {
-        m->device[k] = devices[k];
-        if (hipSetDevice(devices[k]) != hipSuccess) rc = QPP_E_HIP;
-        if (rc == QPP_OK) rc = qpp_session_create(1 << 16, 64, &m->s[k]);
-        if (rc == QPP_OK) rc = qpp_keytab_create(key_capacity, &m->kt[k]);
-        m->n = k + 1;
-    }
-    (void)hipSetDevice(prev);
-    if (rc != QPP_OK) {
-        qpp_multi_destroy(m);
-        return rc;
-    }
-    *out = m;
-    return QPP_OK;
-}
-
-void qpp_multi_destroy(qpp_multi *m)
-{
-    if (!m) return;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    for (int k = 0; k < m->n; ++k) {
-        (void)hipSetDevice(m->device[k]);
-        qpp_session_destroy(m->s[k]);
-        qpp_keytab_destroy(m->kt[k]);
-    }
-    (void)hipSetDevice(prev);
-    free(m);
-}
-
-int qpp_multi_devices(const qpp_multi *m) { return m ? m->n : 0; }
-
-int qpp_multi_set_keys(qpp_multi *m, const qpp_key_material *km, uint32_t n)
-{
-    if (!m) return QPP_E_ARG;
-    int prev = 0, rc = QPP_OK;
-    (void)hipGetDevice(&prev);
-    for (int k = 0; k < m->n && rc == QPP_OK; ++k) {
-        if (hipSetDevice(m->device[k]) != hipSuccess) rc = QPP_E_HIP;
-        if (rc == QPP_OK) rc = qpp_session_set_keys(m->s[k], m->kt[k], km, n);
-        if (rc == QPP_OK) rc = hipStreamSynchronize((hipStream_t)qpp_session_stream(m->s[k])) == hipSuccess
-                                   ? QPP_OK : QPP_E_HIP;
-    }
-    (void)hipSetDevice(prev);
-    return rc;
-}
-
-static int multi_run(bool enc, qpp_multi *m, const qpp_desc *desc, uint32_t n, const uint8_t *in,
-                     size_t in_len, uint8_t *out, size_t out_len, qpp_result *res)
-{
-    if (!m || (n && (!desc || !res))) return QPP_E_ARG;
-    if (n == 0) {
-        if (out_len) memset(out, 0, out_len);
-        return QPP_OK;
-    }
-    if (m->n == 1) {
-        // one device: the session itself (its bounds checks and staging),
-        // without the range split's copy and passes over the descriptors
-        int prev = 0;
-        (void)hipGetDevice(&prev);
-        (void)hipSetDevice(m->device[0]);
-        const int rc = enc ? qpp_session_protect(m->s[0], m->kt[0], desc, n, in, in_len, out, out_len, res)
-                           : qpp_session_unprotect(m->s[0], m->kt[0], desc, n, in, in_len, out, out_len, res);
-        (void)hipSetDevice(prev);
-        return rc;
-    }
-    int parts = m->n < (int)n ? m->n : (int)n;
-    // bounds first (as a session does), so that extents use only packets
-    // that fit; rejected ones stay rejected in their range and touch nothing
-    std::vector<qpp_desc> d(desc, desc + n);
-    reject_out_of_bounds(enc, d.data(), n, in_len, out_len);
-    struct Range {
-        uint32_t b, e;
-        size_t ilo, ihi, olo, ohi;
-    };
-    std::vector<Range> r(parts);
-    for (int k = 0; k < parts; ++k) {
-        Range &x = r[k];
-        x.b = (uint32_t)((uint64_t)n * k / parts);
-        x.e = (uint32_t)((uint64_t)n * (k + 1) / parts);
-        x.ilo = x.olo = SIZE_MAX;
-        x.ihi = x.ohi = 0;
-        for (uint32_t i = x.b; i < x.e; ++i) {
-            if (d[i].flags & kFlagReject) continue;
-            const size_t rd = enc ? (size_t)d[i].hdr_len + d[i].len : d[i].len;
-            const size_t wr = enc ? rd + QPP_TAG_LEN : rd;
-            x.ilo = std::min<size_t>(x.ilo, d[i].in_off);
-            x.ihi = std::max<size_t>(x.ihi, d[i].in_off + rd);
-            x.olo = std::min<size_t>(x.olo, d[i].out_off);
-            x.ohi = std::max<size_t>(x.ohi, d[i].out_off + wr);
-        }
-        if (x.ilo == SIZE_MAX) x.ilo = x.ihi = x.olo = x.ohi = 0;
-    }
-    // ranges in output order with disjoint extents, or one device: every
-    // non-empty range starts at or after the end of all earlier non-empty
-    // ones (an empty range -- every packet rejected -- compares with nothing)
-    size_t seen_hi = 0;
-    bool seen = false;
-    for (int k = 0; k < parts; ++k) {
-        if (r[k].ohi <= r[k].olo) continue;
-        if (seen && seen_hi > r[k].olo) {
-            parts = 1;
-            r.assign(1, Range{0, n, 0, in_len, 0, out_len});
-            break;
-        }
-        seen_hi = std::max(seen_hi, r[k].ohi);
-        seen = true;
-    }
-    if (parts == 1) {
-        int prev = 0;
-        (void)hipGetDevice(&prev);
-        (void)hipSetDevice(m->device[0]);
-        const int rc = enc ? qpp_session_protect(m->s[0], m->kt[0], desc, n, in, in_len, out, out_len, res)
-                           : qpp_session_unprotect(m->s[0], m->kt[0], desc, n, in, in_len, out, out_len, res);
-        (void)hipSetDevice(prev);
-        return rc;
-    }
-    // rebase each range onto its extents
-    for (int k = 0; k < parts; ++k)
-        for (uint32_t i = r[k].b; i < r[k].e; ++i) {
-            if (d[i].flags & kFlagReject) {
-                // past every range buffer: the range's session rejects it again
-                d[i].in_off = d[i].out_off = ~0ull;
-                continue;
-            }
-            d[i].in_off -= r[k].ilo;
-            d[i].out_off -= r[k].olo;
-        }
-    // output bytes outside every range's extent: zeros, as one session leaves them
-    size_t pos = 0;
-    for (int k = 0; k < parts; ++k) {
-        if (r[k].ohi <= r[k].olo) continue;
-        if (r[k].olo > pos) memset(out + pos, 0, r[k].olo - pos);
-        pos = r[k].ohi;
-    }
-    if (out_len > pos) memset(out + pos, 0, out_len - pos);
-    std::vector<int> rcs(parts, QPP_OK);
-    std::vector<std::thread> th;
-    for (int k = 0; k < parts; ++k)
-        th.emplace_back([&, k] {
-            const Range &x = r[k];
-            if (hipSetDevice(m->device[k]) != hipSuccess) {
-                rcs[k] = QPP_E_HIP;
-                return;
-            }
-            const uint32_t cnt = x.e - x.b;
-            rcs[k] = enc ? qpp_session_protect(m->s[k], m->kt[k], d.data() + x.b, cnt, in + x.ilo, x.ihi - x.ilo,
-                                               out + x.olo, x.ohi - x.olo, res + x.b)
-                         : qpp_session_unprotect(m->s[k], m->kt[k], d.data() + x.b, cnt, in + x.ilo, x.ihi - x.ilo,
-                                                 out + x.olo, x.ohi - x.olo, res + x.b);
-        });
-    for (auto &t : th) t.join();
-    for (int k = 0; k < parts; ++k)
-        if (rcs[k] != QPP_OK) return rcs[k];
-    return QPP_OK;
-}
-
-int qpp_multi_protect(qpp_multi *m, const qpp_desc *desc, uint32_t n, const uint8_t *in, size_t in_len,
-                      uint8_t *out, size_t out_len, qpp_result *res)
-{
-    return multi_run(true, m, desc, n, in, in_len, out, out_len, res);
-}
-
-int qpp_multi_unprotect(qpp_multi *m, const qpp_desc *desc, uint32_t n, const uint8_t *in, size_t in_len,
-                        uint8_t *out, size_t out_len, qpp_result *res)
-{
-    return multi_run(false, m, desc, n, in, in_len, out, out_len, res);
-}
-
-int qpp_multi_trace(qpp_multi *m, int enable, qpp_trace *last, int max)
-{
-    if (!m || max < 0 || (max > 0 && !last)) return QPP_E_ARG;
-    int prev = 0, rc = QPP_OK, k = 0;
-    (void)hipGetDevice(&prev);
-    for (; k < m->n && rc == QPP_OK; ++k) {
-        if (hipSetDevice(m->device[k]) != hipSuccess) rc = QPP_E_HIP;
-        if (rc == QPP_OK) rc = qpp_session_trace(m->s[k], enable, k < max ? last + k : nullptr);
-    }
-    (void)hipSetDevice(prev);
-    return rc == QPP_OK ? (m->n < max ? m->n : max) : rc;
-}
-
-}  // extern "C"

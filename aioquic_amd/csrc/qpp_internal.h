@@ -5,7 +5,16 @@
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 
+#include "qpp_batch.h"
 #include "qpp_device.h"
+
+#define HIPCHK(x)                          \
+    do {                                   \
+        if ((x) != hipSuccess) {           \
+            (void)hipGetLastError();       \
+            return QPP_E_HIP;              \
+        }                                  \
+    } while (0)
 
 // The one way the library reads an environment switch: the variable's integer
 // value, or dflt when it is unset or empty.  Every switch is a product or
@@ -52,6 +61,44 @@ int qpp_internal_plan_gather(const qpp_plan *p, const qpp_desc *d_desc, uint32_t
 // wave items of a batch of n packets on a table of `cap` slots, at most
 uint32_t qpp_internal_plan_max_items(uint32_t n, uint32_t cap);
 int qpp_internal_plan_nokey(const qpp_plan *p, qpp_result *d_res, hipStream_t s);
+
+// ---- qpp_engine.hip, for the sessions (qpp_session.hip; qpp_keytab stays
+// opaque to them) ----
+
+namespace qpp {
+
+constexpr int kLoneWG = 1024;      // 16 packets per workgroup, one AES image
+
+// A small host call handed to a lone kernel whole (qpp_session): the kernel
+// copies the call's descriptors and input from the pinned staging (src, its
+// device view) into the device staging (dst) itself, every thread 16 bytes
+// in one bus round trip, instead of a copy-engine blit scheduled between
+// stream operations.  bytes == 0: nothing staged (device-buffer launches).
+// One workgroup (at most 16 packets); the workgroup barrier makes the copy
+// visible to its waves (vector L1 writes through to L2).
+struct LoneStage {
+    const uint8_t *src;
+    uint8_t *dst;
+    uint32_t bytes;  // multiple of 16, <= kLoneStageMax
+};
+constexpr uint32_t kLoneStageMax = 2 * kLoneWG * 16;
+
+}  // namespace qpp
+
+// qpp_protect / qpp_unprotect (enc), over a plan's sorted descriptors when
+// plan is given (qpp_*_planned), staged by the lone kernel when stage is
+int qpp_internal_launch_packets(bool enc, const qpp_keytab *kt, const qpp_desc *d_desc, uint32_t n,
+                                const uint8_t *d_in, uint8_t *d_out, qpp_result *d_res, void *stream,
+                                const qpp_plan *plan = nullptr, const qpp::LoneStage *stage = nullptr);
+// Up to how many packets an unplanned launch takes the lone kernels whatever
+// the suite (0: never, QPP_LONE=0).
+uint32_t qpp_internal_lone_limit();
+// D2H of a session: up to two device ranges (s0, s1) into pinned host memory
+// (device views d0, d1), by k_xfer.
+int qpp_internal_launch_xfer(uint8_t *d0, const uint8_t *s0, size_t n0, uint8_t *d1, const uint8_t *s1,
+                             size_t n1, hipStream_t st);
+
+// ---- qpp_session.hip ----
 
 // A session's buffers for a caller in another translation unit
 // (qpp_session_route_unprotect): the staging reserved for `bytes` of input and

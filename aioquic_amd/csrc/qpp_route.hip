@@ -35,14 +35,6 @@ struct qpp_cidmap {
     uint32_t scatter_cap;
 };
 
-#define HIPCHK(x)                          \
-    do {                                   \
-        if ((x) != hipSuccess) {           \
-            (void)hipGetLastError();       \
-            return QPP_E_HIP;              \
-        }                                  \
-    } while (0)
-
 namespace {
 
 constexpr int kRouteWG = 256;

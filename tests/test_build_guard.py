@@ -72,7 +72,7 @@ def test_import_refuses_mismatched_library(tmp_path):
     assert "come from different builds" in bad.stderr
 
 
-@pytest.mark.parametrize("unit", ["qpp_engine.hip"])
+@pytest.mark.parametrize("unit", ["qpp_engine.hip", "qpp_session.hip"])
 def test_objects_rebuild_on_content_not_time(tmp_path, unit):
     """build.py's staleness is the hash of an object's inputs recorded beside
     it: a file whose mtime moves without a content change is not stale."""

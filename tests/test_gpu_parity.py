@@ -580,7 +580,7 @@ def test_session_pipelined_unaligned_ragged(oracle, L, engine_cls):
                          ids=["3-chunks", "3-chunks-mixed", "tapered-13-chunks"])
 def test_session_pipelined_host_batch(L, engine_cls, mixed, n):
     """Host-buffer batches of >= 64 MiB go through the session's three-stage
-    pipeline (chunked H2D / kernels / D2H, qpp_engine.hip session_run_pipelined;
+    pipeline (chunked H2D / kernels / D2H, qpp_session.hip session_run_pipelined;
     from 8 regular chunks on, the first and last are cut into quarter /
     quarter / half pieces: 262144 packets, 315 MB, run as 13 chunks).
     Its output and results must equal the serial session path

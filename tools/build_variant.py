@@ -5,9 +5,14 @@ in-tree library is left alone):
 
     python tools/build_variant.py NAME [--src FILE | --rev GITREV] -DQPP_SWITCH=0 ...
 
+Every other unit of build.HIP_UNITS is linked as the in-tree build left it,
+except qpp_session.o beside an engine that still defines the sessions itself
+(revisions from before qpp_session.hip).  --rev compiles that revision's
+engine beside today's headers, so it takes revisions that still compile there.
 The variant links the in-tree source-hash object, so the in-tree _crypto
 extension accepts it (a deliberate A/B, not a stale build).
 tools/ab_lib.sh runs the bench against such builds via LD_LIBRARY_PATH."""
+import importlib.util
 import os
 import subprocess
 import sys
@@ -34,10 +39,21 @@ hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 try:
     subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", os.path.join(ROOT, "include"),
                     "-I", os.path.join(ROOT, "aioquic_amd", "csrc"), "-c", "-o", obj] + flags + [src], check=True)
+    with open(src) as f:
+        own_sessions = "qpp_session_create(" in f.read()  # an engine from before qpp_session.hip
 finally:
     if os.path.basename(src).startswith(".variant_"):
         os.remove(src)
-objs = [obj, os.path.join(ROOT, "build", "obj", "qpp_plan.o"), os.path.join(ROOT, "build", "obj", "qpp_source_hash.o")]
+# aioquic_amd/build.py, by its path: the list of units and where their objects are
+spec = importlib.util.spec_from_file_location("qpp_build", os.path.join(ROOT, "aioquic_amd", "build.py"))
+build = importlib.util.module_from_spec(spec)
+spec.loader.exec_module(build)
+skip = {"qpp_engine.hip"} | ({"qpp_session.hip"} if own_sessions else set())
+objs = [obj] + [build._obj(u) for u in build.HIP_UNITS if u not in skip] + \
+    [os.path.join(build.OBJ, "qpp_source_hash.o")]
+missing = [o for o in objs if not os.path.exists(o)]
+if missing:
+    sys.exit("build the tree first (python -m aioquic_amd.build): missing " + ", ".join(missing))
 subprocess.run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", os.path.join(out, "libquicpp.so")] + objs,
                check=True)
 os.remove(obj)

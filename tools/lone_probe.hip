@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../aioquic_amd/csrc/qpp_engine.hip"
+#include "../aioquic_amd/csrc/qpp_session.hip"
 
 #ifndef QPP_PROBE  // without the marks: the calls and their statuses only
 constexpr int kProbeSlots = 16, kProbeStart = 13, kProbeEnd = 14;
