@@ -153,6 +153,33 @@ class PacketEngine:
         return (np.frombuffer(out, dtype=np.uint8), np.frombuffer(desc, dtype=L.DESC),
                 np.frombuffer(route, dtype=L.ROUTE), np.frombuffer(res, dtype=L.RESULT))
 
+    def route_walk(self, cid_len: int, offs, lens, n: int, inbuf, route, long_idx, n_long: int, conn_slot,
+                   conn_expected, n_conn: int, desc, walk, walk_n, flags: int = 0, stream=None) -> None:
+        """qpp_route_walk on device buffers, after route() on the same stream:
+        the header walk of the datagrams `long_idx` (uint32, strictly
+        increasing) into WALK records (4 per listed datagram), `walk_n` counts
+        and DESC records (`desc` holds n + 3 n_long), from `conn_slot`
+        (uint32, n_conn x KEYSETS) and `conn_expected` (uint64, n_conn x SPACES)."""
+        _crypto.route_walk(int(cid_len), _ptr(offs), _ptr(lens), int(n), _ptr(inbuf), _ptr(route), _ptr(long_idx),
+                           int(n_long), _ptr(conn_slot), _ptr(conn_expected), int(n_conn), int(flags), _ptr(desc),
+                           _ptr(walk), _ptr(walk_n), self._stream(stream))
+
+    def route_walk_unprotect_host(self, cid_map, cid_len: int, offs, lens, data, long_idx, conn_slot,
+                                  conn_expected, out_len: int, flags: int = 0):
+        """Route, walk the long-header datagrams `long_idx` and unprotect a
+        host buffer of raw datagrams in one call
+        (qpp_session_route_walk_unprotect).  Returns (out, desc, route,
+        results, walk, walk_n); desc and results hold n + 3 n_long entries."""
+        out, desc, route, res, walk, walk_n = _crypto.route_walk_unprotect_host(
+            self.table, cid_map, int(cid_len), np.ascontiguousarray(offs, dtype=np.uint64).tobytes(),
+            np.ascontiguousarray(lens, dtype=np.uint32).tobytes(), bytes(data),
+            np.ascontiguousarray(long_idx, dtype=np.uint32).tobytes(),
+            np.ascontiguousarray(conn_slot, dtype=np.uint32).tobytes(),
+            np.ascontiguousarray(conn_expected, dtype=np.uint64).tobytes(), int(flags), int(out_len))
+        return (np.frombuffer(out, dtype=np.uint8), np.frombuffer(desc, dtype=L.DESC),
+                np.frombuffer(route, dtype=L.ROUTE), np.frombuffer(res, dtype=L.RESULT),
+                np.frombuffer(walk, dtype=L.WALK).reshape(-1, L.WALK_MAX), np.frombuffer(walk_n, dtype=np.uint32))
+
     # ----------------------------------------------- host-buffer forms ----
 
     def protect_host(self, desc: np.ndarray, data, out_len: int):

@@ -46,7 +46,7 @@ import numpy as np
 
 from . import crypto as crypto_mod
 from . import layout as L
-from ._crypto import CryptoError, KeyTable, protect_list, unprotect_list, unprotect_walk
+from ._crypto import CryptoError, KeyTable, protect_list, unprotect_list, unprotect_walk, walk_results
 from .crypto import CryptoContext, CryptoPair, KeyUnavailableError, next_key_phase
 from .packet import decode_packet_number
 
@@ -471,6 +471,7 @@ class ReceiveBatch:
         self._conns: list = []  # connection key per item (None: none)
         self._rsv: list = []    # reserved-bit mask per item (0: no check)
         self._closed: set = set()  # connections closed by the walk so far
+        self._pre = None           # results of a launch that has run already (preset)
         self.launches = 0
 
     def __len__(self) -> int:
@@ -496,16 +497,27 @@ class ReceiveBatch:
         return len(self._pairs) - 1
 
     def _extend(self, pairs: list, packets: list, offs: list, spaces: list, conns: Optional[list] = None,
-                rsv: int = 0) -> None:
+                rsv=0) -> None:
         """add() for many packets at once, each with a tracked space (the
-        batched receive walk's form: packets are bytes, no copies)."""
+        batched receive walk's form: packets are bytes, no copies).  `rsv`:
+        one reserved-bit mask for all, or a list of one per packet."""
         self._pairs += pairs
         self._packets += packets
         self._offs += offs
         self._spaces += spaces
         self._track += [True] * len(pairs)
         self._conns += conns if conns is not None else [None] * len(pairs)
-        self._rsv += [rsv] * len(pairs)
+        self._rsv += list(rsv) if isinstance(rsv, (list, tuple)) else [rsv] * len(pairs)
+
+    def preset(self, desc: bytes, results: bytes, dix, out: bytes) -> None:
+        """The first round's launch has run already (receive_routed's fused
+        route + walk + unprotect): item i's descriptor and result are
+        desc / results [dix[i]] (packed layout.DESC / RESULT) and its output
+        lies in `out` at the descriptor's out_off.  Each item was decoded
+        against its space's expected number as it stands now, with its pair's
+        current receive key.  run() then walks these results instead of
+        launching; only what that walk defers is launched."""
+        self._pre = (desc, results, np.ascontiguousarray(dix, dtype=np.uint32).tobytes(), out)
 
     def _fast_round(self, outcome: list) -> list:
         """The first round in C (_crypto.unprotect_walk): one launch and the
@@ -534,20 +546,28 @@ class ReceiveBatch:
             uspaces[k] = sp
         keyed = [k for k, p in enumerate(upairs) if p.recv.aead is not None]
         pslot = np.full(len(upairs), 0xFFFFFFFF, np.uint32)
-        if keyed:
+        pre = self._pre
+        if keyed and pre is not None:
+            pslot[keyed] = 0  # the walk only asks whether there is a key
+        elif keyed:
             keys = _KeyRefs()
             prefs = [keys.ref(upairs[k].recv.aead, upairs[k].recv.hp, upairs[k].recv.key_phase) for k in keyed]
             pslot[keyed] = np.asarray(self.slots.assign(keys.triples), dtype=np.uint32)[np.asarray(prefs, np.int64)]
         p_arr = np.asarray(p_of, dtype=np.uint32)
         s_arr = np.asarray(s_of, dtype=np.uint32)
         sexp = np.asarray([sp.expected_packet_number & 0xFFFFFFFFFFFFFFFF for sp in uspaces], dtype=np.uint64)
-        outs, res, deferred, sexp2, closed = unprotect_walk(
-            self.slots.table, pslot[p_arr].tobytes(), sexp[s_arr].tobytes(), self._packets,
-            np.asarray([min(o, 0xFFFF) for o in offs], np.uint32).tobytes(),
-            p_arr.tobytes(), s_arr.tobytes(), np.asarray(track, np.uint8).tobytes(),
-            sexp.tobytes(), len(upairs), np.asarray(c_of, np.uint32).tobytes(),
-            np.asarray(self._rsv, np.uint8).tobytes(), bytes(len(cix)))
-        self.launches += 1
+        per_item = (np.asarray([min(o, 0xFFFF) for o in offs], np.uint32).tobytes(),
+                    p_arr.tobytes(), s_arr.tobytes(), np.asarray(track, np.uint8).tobytes(),
+                    sexp.tobytes(), len(upairs), np.asarray(c_of, np.uint32).tobytes(),
+                    np.asarray(self._rsv, np.uint8).tobytes(), bytes(len(cix)))
+        if pre is not None:
+            self._pre = None
+            outs, res, deferred, sexp2, closed = walk_results(pslot[p_arr].tobytes(), sexp[s_arr].tobytes(),
+                                                              *per_item, *pre)
+        else:
+            outs, res, deferred, sexp2, closed = unprotect_walk(
+                self.slots.table, pslot[p_arr].tobytes(), sexp[s_arr].tobytes(), self._packets, *per_item)
+            self.launches += 1
         # outcomes: successes come as (header, payload, pn); failures by status
         st = np.frombuffer(res, dtype=L.RESULT)["status"]
         fail = np.flatnonzero(st != L.S_OK)

@@ -1136,6 +1136,100 @@ static PyObject *py_route_unprotect_host(PyObject *m, PyObject *args)
     return ret;
 }
 
+/* route_walk(cid_len, off_ptr, len_ptr, n, in_ptr, route_ptr, long_ptr, n_long, slot_ptr, exp_ptr, n_conn, flags,
+ *            desc_ptr, walk_ptr, walk_n_ptr, stream) */
+static PyObject *py_route_walk(PyObject *m, PyObject *args)
+{
+    unsigned long long op, lp, ip, rp, xp, slp, ep, dp, wp, wnp, sp;
+    unsigned int cid_len, n, n_long, n_conn, flags;
+    if (!PyArg_ParseTuple(args, "IKKIKKKIKKIIKKKK", &cid_len, &op, &lp, &n, &ip, &rp, &xp, &n_long, &slp, &ep, &n_conn,
+                          &flags, &dp, &wp, &wnp, &sp))
+        return NULL;
+    if (flags > 0xffff) {
+        PyErr_SetString(PyExc_ValueError, "descriptor flags are 16 bits");
+        return NULL;
+    }
+    int rc = qpp_route_walk(cid_len, as_ptr(op), as_ptr(lp), n, as_ptr(ip), as_ptr(rp), as_ptr(xp), n_long,
+                            as_ptr(slp), as_ptr(ep), n_conn, (uint16_t)flags, as_ptr(dp), as_ptr(wp), as_ptr(wnp),
+                            as_ptr(sp));
+    if (rc == QPP_E_ARG) {
+        PyErr_SetString(PyExc_ValueError, "bad route_walk arguments (cid_len outside 1..20, n_long > n, or a null "
+                                          "buffer)");
+        return NULL;
+    }
+    if (check_rc(rc) < 0) return NULL;
+    Py_RETURN_NONE;
+}
+
+/* route_walk_unprotect_host(table, map, cid_len, offs_u64, lens_u32, data, long_idx_u32, conn_slot_u32 (x KEYSETS),
+ *                           conn_expected_u64 (x SPACES), flags, out_len)
+ *     -> (out, desc, route, results, walk, walk_n) */
+static PyObject *py_route_walk_unprotect_host(PyObject *m, PyObject *args)
+{
+    PyObject *t, *mo;
+    const char *offs, *lens, *data, *lidx, *cslot, *cexp;
+    Py_ssize_t l_offs, l_lens, l_data, l_lidx, l_cslot, l_cexp, out_len;
+    unsigned int cid_len, flags;
+    if (!PyArg_ParseTuple(args, "OOIy#y#y#y#y#y#In", &t, &mo, &cid_len, &offs, &l_offs, &lens, &l_lens, &data, &l_data,
+                          &lidx, &l_lidx, &cslot, &l_cslot, &cexp, &l_cexp, &flags, &out_len))
+        return NULL;
+    qpp_keytab *kt = as_table(t);
+    qpp_cidmap *map = kt ? as_cidmap(mo) : NULL;
+    if (!map) return NULL;
+    const Py_ssize_t n = l_lens / 4, nl = l_lidx / 4, nc = l_cslot / (4 * QPP_KEYSETS);
+    if (l_lens % 4 || l_lidx % 4 || l_cslot != nc * 4 * QPP_KEYSETS || l_offs != n * 8 ||
+        l_cexp != nc * 8 * QPP_SPACES || out_len < 0 || flags > 0xffff || n > 0x7fffffff || nc > 0x7fffffff ||
+        nl > 0x7fffffff || n + 3 * nl > 0x7fffffff) {
+        PyErr_SetString(PyExc_ValueError, "bad array lengths, flags or output length");
+        return NULL;
+    }
+    const Py_ssize_t nd = n + 3 * nl;
+    PyObject *out = PyBytes_FromStringAndSize(NULL, out_len);
+    PyObject *desc = PyBytes_FromStringAndSize(NULL, nd * (Py_ssize_t)sizeof(qpp_desc));
+    PyObject *route = PyBytes_FromStringAndSize(NULL, n * (Py_ssize_t)sizeof(qpp_route_rec));
+    PyObject *res = PyBytes_FromStringAndSize(NULL, nd * (Py_ssize_t)sizeof(qpp_result));
+    PyObject *walk = PyBytes_FromStringAndSize(NULL, nl * QPP_WALK_MAX * (Py_ssize_t)sizeof(qpp_walk_rec));
+    PyObject *walk_n = PyBytes_FromStringAndSize(NULL, nl * 4);
+    PyObject *ret = NULL;
+    qpp_session *s = out && desc && route && res && walk && walk_n ? session() : NULL;
+    if (s) {
+        char *o = PyBytes_AsString(out);
+        /* an empty batch, or a refused one, leaves `out` as zeros */
+        memset(o, 0, (size_t)out_len);
+        memset(PyBytes_AsString(walk), 0, (size_t)PyBytes_Size(walk)); /* a refused call leaves zeros */
+        int rc;
+        Py_BEGIN_ALLOW_THREADS
+        rc = qpp_session_route_walk_unprotect(s, kt, map, cid_len, (const uint64_t *)offs, (const uint32_t *)lens,
+                                              (uint32_t)n, (const uint8_t *)data, (size_t)l_data,
+                                              (const uint32_t *)lidx, (uint32_t)nl, (const uint32_t *)cslot,
+                                              (const uint64_t *)cexp, (uint32_t)nc, (uint16_t)flags, (uint8_t *)o,
+                                              (size_t)out_len, (qpp_desc *)PyBytes_AsString(desc),
+                                              (qpp_route_rec *)PyBytes_AsString(route),
+                                              (qpp_result *)PyBytes_AsString(res),
+                                              (qpp_walk_rec *)PyBytes_AsString(walk),
+                                              (uint32_t *)PyBytes_AsString(walk_n));
+        Py_END_ALLOW_THREADS
+        if (rc == QPP_E_ARG)
+            PyErr_SetString(PyExc_ValueError, "bad route arguments (cid_len outside 1..20, a datagram outside the "
+                                              "input or the output buffer, or long_idx not strictly increasing "
+                                              "below n); nothing was launched");
+        else if (check_rc(rc) == 0)
+            ret = PyTuple_Pack(6, out, desc, route, res, walk, walk_n);
+    }
+    Py_XDECREF(out);
+    Py_XDECREF(desc);
+    Py_XDECREF(route);
+    Py_XDECREF(res);
+    Py_XDECREF(walk);
+    Py_XDECREF(walk_n);
+    return ret;
+}
+
+static PyObject *py_route_walk_launches(PyObject *m, PyObject *unused)
+{
+    return PyLong_FromUnsignedLongLong(qpp_route_walk_launches());
+}
+
 static int host_call(int enc, qpp_keytab *kt, const void *desc, uint32_t n, const void *in,
                      size_t in_len, void *out, size_t out_len, void *res)
 {
@@ -1505,6 +1599,87 @@ static int64_t decode_pn_signed(uint64_t pn, int pn_len, uint64_t expected)
     return r < 0 ? -1 : r;
 }
 
+/* The in-order walk of unprotect_walk / walk_results over the results of one
+ * launch: r[i] (statuses rewritten in place) and the output of packet i at
+ * hout + out_off[i]. */
+typedef struct {
+    Py_ssize_t n;
+    const uint32_t *slots, *offs, *pair, *space, *conn;
+    const uint64_t *exp, *out_off;
+    const uint8_t *track, *rsv, *hout;
+    uint64_t *sx;
+    uint8_t *closed, *blocked_pair, *blocked_space, *blocked_conn;
+    PyObject *outs, *deferred;
+} ResultsWalk;
+
+static int results_walk(const ResultsWalk *w, qpp_result *r)
+{
+    const Py_ssize_t n = w->n;
+    const uint32_t *slots = w->slots, *offs = w->offs, *pair = w->pair, *space = w->space, *conn = w->conn;
+    const uint64_t *exp = w->exp, *out_off = w->out_off;
+    const uint8_t *track = w->track, *rsv = w->rsv, *hout = w->hout;
+    uint64_t *sx = w->sx;
+    uint8_t *closed = w->closed, *blocked_pair = w->blocked_pair, *blocked_space = w->blocked_space;
+    uint8_t *blocked_conn = w->blocked_conn;
+    PyObject *outs = w->outs, *deferred = w->deferred;
+    /* no receive key (crypto.py:78-79) and packet-number offsets past the
+       header limit fail whatever the launch left in their results */
+    for (Py_ssize_t i = 0; i < n; ++i) {
+        if (slots[i] == 0xffffffffu) r[i].status = QPP_S_NO_KEY;
+        else if (offs[i] > QPP_MAX_HDR) r[i].status = QPP_S_LENGTH;
+    }
+    for (Py_ssize_t i = 0; i < n; ++i) {
+        const uint32_t p = pair[i], sp = space[i], c = conn[i];
+        PyObject *item = Py_None;
+        Py_INCREF(Py_None);
+        PyList_SetItem(outs, i, item);
+        int defer = blocked_pair[p] || blocked_space[sp] || (c != WALK_NO_CONN && blocked_conn[c]);
+        if (!defer && c != WALK_NO_CONN && closed[c]) {
+            r[i].status = WALK_S_CLOSED; /* connection.py:756-757 */
+            continue;
+        }
+        const uint16_t st = r[i].status;
+        const uint64_t now = sx[sp];
+        if (!defer && st == QPP_S_KEY_PHASE) defer = 1;
+        if (!defer && now != exp[i] && (st == QPP_S_OK || st == QPP_S_DECRYPT)) {
+            const int pn_len = (int)r[i].hdr_len - (int)offs[i];
+            if (pn_len < 1 || pn_len > 4 || decode_pn_signed(r[i].pn, pn_len, now) != (int64_t)r[i].pn) defer = 1;
+        }
+        if (defer) {
+            blocked_pair[p] = blocked_space[sp] = 1;
+            if (c != WALK_NO_CONN) blocked_conn[c] = 1;
+            PyObject *ix = PyLong_FromSsize_t(i);
+            if (!ix || PyList_Append(deferred, ix) < 0) {
+                Py_XDECREF(ix);
+                return -1;
+            }
+            Py_DECREF(ix);
+            continue;
+        }
+        if (st != QPP_S_OK) continue;
+        const uint8_t *o = hout + out_off[i];
+        if (rsv[i] && r[i].hdr_len && (o[0] & rsv[i])) {
+            /* connection.py:949-960: close, end, no expected-number update */
+            r[i].status = WALK_S_RESERVED;
+            if (c != WALK_NO_CONN) closed[c] = 1;
+            continue;
+        }
+        PyObject *h = PyBytes_FromStringAndSize((const char *)o, r[i].hdr_len);
+        PyObject *pl = PyBytes_FromStringAndSize((const char *)o + r[i].hdr_len,
+                                                 (Py_ssize_t)r[i].out_len - r[i].hdr_len);
+        PyObject *pn = PyLong_FromUnsignedLongLong(r[i].pn);
+        item = (h && pl && pn) ? PyTuple_Pack(3, h, pl, pn) : NULL;
+        Py_XDECREF(h);
+        Py_XDECREF(pl);
+        Py_XDECREF(pn);
+        if (!item) return -1;
+        PyObject_GC_UnTrack(item); /* bytes and an int: never in a cycle (make_record) */
+        PyList_SetItem(outs, i, item);
+        if (track[i] && r[i].pn > now) sx[sp] = r[i].pn + 1;
+    }
+    return 0;
+}
+
 /* unprotect_walk(table, slots_u32, exp_u64, packets, offs_u32, pair_u32,
  *                space_u32, track_u8, space_exp_u64, n_pairs, conn_u32,
  *                rsv_u8, closed_u8)
@@ -1557,6 +1732,7 @@ static PyObject *py_unprotect_walk(PyObject *m, PyObject *args)
     const uint8_t *track = (const uint8_t *)a_track, *rsv = (const uint8_t *)a_rsv;
     PyObject *ret = NULL, *outs = NULL, *res = NULL, *deferred = NULL, *sexp_out = NULL, *closed_out = NULL;
     qpp_desc *desc = NULL;
+    uint64_t *out_off = NULL;
     uint8_t *blocked_pair = NULL, *blocked_space = NULL, *blocked_conn = NULL;
     sexp_out = PyBytes_FromStringAndSize(a_sexp, l_sexp);  /* the spaces' expected numbers, advanced below */
     closed_out = PyBytes_FromStringAndSize(a_closed, l_closed); /* the connections' closed flags, set below */
@@ -1580,13 +1756,14 @@ static PyObject *py_unprotect_walk(PyObject *m, PyObject *args)
         total += (size_t)PyBytes_Size(o);
     }
     desc = (qpp_desc *)calloc(n ? (size_t)n : 1, sizeof(qpp_desc));
+    out_off = (uint64_t *)calloc(n ? (size_t)n : 1, sizeof(uint64_t));
     res = PyBytes_FromStringAndSize(NULL, n * (Py_ssize_t)sizeof(qpp_result));
     blocked_pair = (uint8_t *)calloc(n_pairs ? n_pairs : 1, 1);
     blocked_space = (uint8_t *)calloc(n_spaces ? (size_t)n_spaces : 1, 1);
     blocked_conn = (uint8_t *)calloc(n_conns ? (size_t)n_conns : 1, 1);
     outs = PyList_New(n);
     deferred = PyList_New(0);
-    if (!desc || !res || !blocked_pair || !blocked_space || !blocked_conn || !outs || !deferred) {
+    if (!desc || !out_off || !res || !blocked_pair || !blocked_space || !blocked_conn || !outs || !deferred) {
         PyErr_NoMemory();
         goto done;
     }
@@ -1600,7 +1777,7 @@ static PyObject *py_unprotect_walk(PyObject *m, PyObject *args)
             const size_t l = (size_t)PyBytes_Size(o);
             memcpy(hin + off, PyBytes_AsString(o), l);
             qpp_desc *d = &desc[i];
-            d->in_off = d->out_off = off;
+            d->in_off = d->out_off = out_off[i] = off;
             d->len = (uint32_t)l;
             d->hdr_len = offs[i] > 0xffff ? 0xffff : (uint16_t)offs[i];
             d->pn = exp[i];
@@ -1610,62 +1787,9 @@ static PyObject *py_unprotect_walk(PyObject *m, PyObject *args)
         if (host_call(0, kt, desc, (uint32_t)n, hin, total, hout, total, PyBytes_AsString(res)) < 0) goto done;
     }
     {
-        qpp_result *r = (qpp_result *)PyBytes_AsString(res);
-        /* no receive key (crypto.py:78-79) and packet-number offsets past the
-           header limit fail whatever the launch left in their results */
-        for (Py_ssize_t i = 0; i < n; ++i) {
-            if (slots[i] == 0xffffffffu) r[i].status = QPP_S_NO_KEY;
-            else if (offs[i] > QPP_MAX_HDR) r[i].status = QPP_S_LENGTH;
-        }
-        for (Py_ssize_t i = 0; i < n; ++i) {
-            const uint32_t p = pair[i], sp = space[i], c = conn[i];
-            PyObject *item = Py_None;
-            Py_INCREF(Py_None);
-            PyList_SetItem(outs, i, item);
-            int defer = blocked_pair[p] || blocked_space[sp] || (c != WALK_NO_CONN && blocked_conn[c]);
-            if (!defer && c != WALK_NO_CONN && closed[c]) {
-                r[i].status = WALK_S_CLOSED; /* connection.py:756-757 */
-                continue;
-            }
-            const uint16_t st = r[i].status;
-            const uint64_t now = sx[sp];
-            if (!defer && st == QPP_S_KEY_PHASE) defer = 1;
-            if (!defer && now != exp[i] && (st == QPP_S_OK || st == QPP_S_DECRYPT)) {
-                const int pn_len = (int)r[i].hdr_len - (int)offs[i];
-                if (pn_len < 1 || pn_len > 4 || decode_pn_signed(r[i].pn, pn_len, now) != (int64_t)r[i].pn) defer = 1;
-            }
-            if (defer) {
-                blocked_pair[p] = blocked_space[sp] = 1;
-                if (c != WALK_NO_CONN) blocked_conn[c] = 1;
-                PyObject *ix = PyLong_FromSsize_t(i);
-                if (!ix || PyList_Append(deferred, ix) < 0) {
-                    Py_XDECREF(ix);
-                    goto done;
-                }
-                Py_DECREF(ix);
-                continue;
-            }
-            if (st != QPP_S_OK) continue;
-            const uint8_t *o = hout + desc[i].out_off;
-            if (rsv[i] && r[i].hdr_len && (o[0] & rsv[i])) {
-                /* connection.py:949-960: close, end, no expected-number update */
-                r[i].status = WALK_S_RESERVED;
-                if (c != WALK_NO_CONN) closed[c] = 1;
-                continue;
-            }
-            PyObject *h = PyBytes_FromStringAndSize((const char *)o, r[i].hdr_len);
-            PyObject *pl = PyBytes_FromStringAndSize((const char *)o + r[i].hdr_len,
-                                                     (Py_ssize_t)r[i].out_len - r[i].hdr_len);
-            PyObject *pn = PyLong_FromUnsignedLongLong(r[i].pn);
-            item = (h && pl && pn) ? PyTuple_Pack(3, h, pl, pn) : NULL;
-            Py_XDECREF(h);
-            Py_XDECREF(pl);
-            Py_XDECREF(pn);
-            if (!item) goto done;
-            PyObject_GC_UnTrack(item); /* bytes and an int: never in a cycle (make_record) */
-            PyList_SetItem(outs, i, item);
-            if (track[i] && r[i].pn > now) sx[sp] = r[i].pn + 1;
-        }
+        const ResultsWalk w = {n, slots, offs, pair, space, conn, exp, out_off, track, rsv, hout, sx, closed,
+                               blocked_pair, blocked_space, blocked_conn, outs, deferred};
+        if (results_walk(&w, (qpp_result *)PyBytes_AsString(res)) < 0) goto done;
     }
     ret = PyTuple_Pack(5, outs, res, deferred, sexp_out, closed_out);
 done:
@@ -1675,6 +1799,97 @@ done:
     Py_XDECREF(res);
     Py_XDECREF(deferred);
     free(desc);
+    free(out_off);
+    free(blocked_pair);
+    free(blocked_space);
+    free(blocked_conn);
+    return ret;
+}
+
+/* walk_results(slots_u32, exp_u64, offs_u32, pair_u32, space_u32, track_u8,
+ *              space_exp_u64, n_pairs, conn_u32, rsv_u8, closed_u8,
+ *              desc, results, dix_u32, out)
+ *     -> what unprotect_walk returns
+ * unprotect_walk's in-order walk over a launch that has run already
+ * (receive_routed's fused route + walk + unprotect): packet i's descriptor and
+ * result are desc / results [dix[i]] and its output lies at out + its
+ * descriptor's out_off.  Nothing is launched.  slots[i] only says whether the
+ * packet's pair has a receive key (0xffffffff: none); exp[i] is the expected
+ * number the launch decoded against. */
+static PyObject *py_walk_results(PyObject *m, PyObject *args)
+{
+    const char *a_sl, *a_exp, *a_offs, *a_pair, *a_space, *a_track, *a_sexp, *a_conn, *a_rsv, *a_closed;
+    const char *a_desc, *a_res, *a_dix, *a_out;
+    Py_ssize_t l_sl, l_exp, l_offs, l_pair, l_space, l_track, l_sexp, l_conn, l_rsv, l_closed;
+    Py_ssize_t l_desc, l_res, l_dix, l_out;
+    unsigned int n_pairs;
+    if (!PyArg_ParseTuple(args, "y#y#y#y#y#y#y#Iy#y#y#y#y#y#y#", &a_sl, &l_sl, &a_exp, &l_exp, &a_offs, &l_offs, &a_pair,
+                          &l_pair, &a_space, &l_space, &a_track, &l_track, &a_sexp, &l_sexp, &n_pairs, &a_conn,
+                          &l_conn, &a_rsv, &l_rsv, &a_closed, &l_closed, &a_desc, &l_desc, &a_res, &l_res, &a_dix,
+                          &l_dix, &a_out, &l_out))
+        return NULL;
+    const Py_ssize_t n = l_dix / 4, nd = l_desc / (Py_ssize_t)sizeof(qpp_desc);
+    if (l_dix % 4 || l_desc % (Py_ssize_t)sizeof(qpp_desc) || l_res != nd * (Py_ssize_t)sizeof(qpp_result)) {
+        PyErr_SetString(PyExc_ValueError, "dix: whole u32 items; desc and results: as many whole records");
+        return NULL;
+    }
+    if (check_len(l_sl, n, 4, "slots") < 0 || check_len(l_exp, n, 8, "exp") < 0 ||
+        check_len(l_offs, n, 4, "offs") < 0 || check_len(l_pair, n, 4, "pair") < 0 ||
+        check_len(l_space, n, 4, "space") < 0 || check_len(l_track, n, 1, "track") < 0 ||
+        check_len(l_conn, n, 4, "conn") < 0 || check_len(l_rsv, n, 1, "rsv") < 0 || l_sexp % 8)
+        return l_sexp % 8 ? (PyErr_SetString(PyExc_ValueError, "space_exp: whole u64 items"), NULL) : NULL;
+    const Py_ssize_t n_spaces = l_sexp / 8, n_conns = l_closed;
+    const uint32_t *pair = (const uint32_t *)a_pair, *space = (const uint32_t *)a_space,
+                   *conn = (const uint32_t *)a_conn, *dix = (const uint32_t *)a_dix;
+    const qpp_desc *desc = (const qpp_desc *)a_desc;
+    const qpp_result *rin = (const qpp_result *)a_res;
+    PyObject *ret = NULL, *outs = NULL, *res = NULL, *deferred = NULL, *sexp_out = NULL, *closed_out = NULL;
+    uint64_t *out_off = (uint64_t *)calloc(n ? (size_t)n : 1, sizeof(uint64_t));
+    uint8_t *blocked_pair = (uint8_t *)calloc(n_pairs ? n_pairs : 1, 1);
+    uint8_t *blocked_space = (uint8_t *)calloc(n_spaces ? (size_t)n_spaces : 1, 1);
+    uint8_t *blocked_conn = (uint8_t *)calloc(n_conns ? (size_t)n_conns : 1, 1);
+    sexp_out = PyBytes_FromStringAndSize(a_sexp, l_sexp);
+    closed_out = PyBytes_FromStringAndSize(a_closed, l_closed);
+    res = PyBytes_FromStringAndSize(NULL, n * (Py_ssize_t)sizeof(qpp_result));
+    outs = PyList_New(n);
+    deferred = PyList_New(0);
+    if (!out_off || !blocked_pair || !blocked_space || !blocked_conn || !sexp_out || !closed_out || !res || !outs ||
+        !deferred) {
+        PyErr_NoMemory();
+        goto done;
+    }
+    qpp_result *r = (qpp_result *)PyBytes_AsString(res);
+    for (Py_ssize_t i = 0; i < n; ++i) {
+        if (pair[i] >= n_pairs || (Py_ssize_t)space[i] >= n_spaces ||
+            (conn[i] != WALK_NO_CONN && (Py_ssize_t)conn[i] >= n_conns) || (Py_ssize_t)dix[i] >= nd) {
+            PyErr_SetString(PyExc_ValueError, "pair, space, connection or descriptor index out of range");
+            goto done;
+        }
+        r[i] = rin[dix[i]];
+        out_off[i] = desc[dix[i]].out_off;
+        /* a success lies inside the output: header and payload are copied from there */
+        if (r[i].status == QPP_S_OK && (out_off[i] > (uint64_t)l_out || r[i].out_len > (uint64_t)l_out - out_off[i] ||
+                                        r[i].hdr_len > r[i].out_len)) {
+            PyErr_SetString(PyExc_ValueError, "a result outside the output");
+            goto done;
+        }
+    }
+    {
+        const ResultsWalk w = {n, (const uint32_t *)a_sl, (const uint32_t *)a_offs, pair, space, conn,
+                               (const uint64_t *)a_exp, out_off, (const uint8_t *)a_track, (const uint8_t *)a_rsv,
+                               (const uint8_t *)a_out, (uint64_t *)PyBytes_AsString(sexp_out),
+                               (uint8_t *)PyBytes_AsString(closed_out), blocked_pair, blocked_space, blocked_conn, outs,
+                               deferred};
+        if (results_walk(&w, r) < 0) goto done;
+    }
+    ret = PyTuple_Pack(5, outs, res, deferred, sexp_out, closed_out);
+done:
+    Py_XDECREF(sexp_out);
+    Py_XDECREF(closed_out);
+    Py_XDECREF(outs);
+    Py_XDECREF(res);
+    Py_XDECREF(deferred);
+    free(out_off);
     free(blocked_pair);
     free(blocked_space);
     free(blocked_conn);
@@ -2099,9 +2314,11 @@ done:
 }
 
 /* receive_routed(table, map, cid_len, datagrams, conn_pair_u32, conn_space_u32,
- *                pair_slot_u32, space_exp_u64, rec_type, packet_type, epoch,
- *                conn_closed_u8, walk)
- *     -> (route, None) | (route, (records, deferred, space_exp after, conn_closed after))
+ *                pair_slot_u32, space_exp_u64, conn_keyset_slot_u32, conn_space_exp_u64,
+ *                rec_type, packet_type, epoch, conn_closed_u8, walk)
+ *     -> (route, None, None)
+ *      | (route, (records, deferred, space_exp after, conn_closed after), None)
+ *      | (route, None, (long_idx, walk records, walk counts, descriptors, results, output))
  * receive_short for datagrams nobody has demultiplexed: `datagrams` is a list
  * of bytes, and the connection of each comes from the route records of one
  * qpp_session_route_unprotect call over the staged batch (its routing kernel
@@ -2111,18 +2328,29 @@ done:
  * the same in-order walk as receive_short, over the QPP_R_SHORT datagrams
  * only: records[j] is the j-th of them, its .datagram the caller's index;
  * `deferred` holds positions j.  `route` is the batch's packed qpp_route_rec.
- * No walk (None, nothing of the state consulted again) with walk == 0 or when
- * a long-header datagram belongs to a known connection: the caller's general
- * path takes the batch then. */
+ * With the walk's arrays given (conn_keyset_slot: QPP_KEYSETS slots per
+ * connection, conn_space_exp: QPP_SPACES expected numbers; both empty: not
+ * given) and walk != 0, the datagrams whose first byte has bit 7 set are
+ * listed while the batch is staged, and the call is
+ * qpp_session_route_walk_unprotect: the device walks their headers in the
+ * same call.  If one of them belongs to a known connection, the third item
+ * carries what the device found -- the listed indices, the qpp_walk_rec and
+ * count arrays, all n + 3 x listed descriptors and results and the output
+ * bytes -- and the caller runs policy and the in-order walk over it
+ * (walk_results) without another launch.
+ * No walk (None, nothing of the state consulted again) with walk == 0, or
+ * when a long-header datagram belongs to a known connection and the walk's
+ * arrays were not given: the caller's general path takes the batch then. */
 static PyObject *py_receive_routed(PyObject *m, PyObject *args)
 {
     PyObject *t, *mo, *dgs, *rec_type, *ptype, *epoch;
-    const char *a_pair, *a_space, *a_pslot, *a_sexp, *a_closed;
-    Py_ssize_t l_pair, l_space, l_pslot, l_sexp, l_closed;
+    const char *a_pair, *a_space, *a_pslot, *a_sexp, *a_closed, *a_kslot, *a_kexp;
+    Py_ssize_t l_pair, l_space, l_pslot, l_sexp, l_closed, l_kslot, l_kexp;
     unsigned int cid_len;
     int walk;
-    if (!PyArg_ParseTuple(args, "OOIO!y#y#y#y#OOOy#i", &t, &mo, &cid_len, &PyList_Type, &dgs, &a_pair, &l_pair,
-                          &a_space, &l_space, &a_pslot, &l_pslot, &a_sexp, &l_sexp, &rec_type, &ptype, &epoch,
+    if (!PyArg_ParseTuple(args, "OOIO!y#y#y#y#y#y#OOOy#i", &t, &mo, &cid_len, &PyList_Type, &dgs, &a_pair, &l_pair,
+                          &a_space, &l_space, &a_pslot, &l_pslot, &a_sexp, &l_sexp, &a_kslot, &l_kslot, &a_kexp,
+                          &l_kexp, &rec_type, &ptype, &epoch,
                           &a_closed, &l_closed, &walk))
         return NULL;
     qpp_keytab *kt = as_table(t);
@@ -2139,6 +2367,11 @@ static PyObject *py_receive_routed(PyObject *m, PyObject *args)
     const Py_ssize_t n = PyList_Size(dgs), nc = l_closed;
     const Py_ssize_t n_pairs = l_pslot / 4, n_spaces = l_sexp / 8;
     if (check_len(l_pair, nc, 4, "conn_pair") < 0 || check_len(l_space, nc, 4, "conn_space") < 0) return NULL;
+    /* the walk's per-key-set and per-space arrays: both or neither */
+    const int can_walk = l_kslot || l_kexp || nc == 0;
+    if (can_walk && (check_len(l_kslot, nc, 4 * QPP_KEYSETS, "conn_keyset_slot") < 0 ||
+                     check_len(l_kexp, nc, 8 * QPP_SPACES, "conn_space_exp") < 0))
+        return NULL;
     const uint32_t *cpair = (const uint32_t *)a_pair, *cspace = (const uint32_t *)a_space,
                    *pslot = (const uint32_t *)a_pslot;
     for (Py_ssize_t c = 0; c < nc; ++c)
@@ -2161,9 +2394,11 @@ static PyObject *py_receive_routed(PyObject *m, PyObject *args)
     uint64_t *offs = (uint64_t *)malloc(n1 * sizeof(uint64_t)), *cexp = (uint64_t *)malloc(nc1 * sizeof(uint64_t));
     uint32_t *lens = (uint32_t *)malloc(n1 * sizeof(uint32_t)), *cslot = (uint32_t *)malloc(nc1 * sizeof(uint32_t));
     uint32_t *conn_of = (uint32_t *)malloc(n1 * sizeof(uint32_t)), *slot_of = (uint32_t *)malloc(n1 * sizeof(uint32_t));
-    uint32_t *dg = (uint32_t *)malloc(n1 * sizeof(uint32_t));
-    qpp_desc *desc = (qpp_desc *)malloc(n1 * sizeof(qpp_desc));
-    qpp_result *res = (qpp_result *)malloc(n1 * sizeof(qpp_result));
+    uint32_t *dg = (uint32_t *)malloc(n1 * sizeof(uint32_t)), *lidx = (uint32_t *)malloc(n1 * sizeof(uint32_t));
+    qpp_desc *desc = NULL;
+    qpp_result *res = NULL;
+    qpp_walk_rec *wrec = NULL;
+    uint32_t *wn = NULL;
     uint8_t **cd = (uint8_t **)malloc(n1 * sizeof(uint8_t *));
     const uint8_t **cs = (const uint8_t **)malloc(n1 * sizeof(uint8_t *));
     size_t *cl = (size_t *)malloc(n1 * sizeof(size_t));
@@ -2175,11 +2410,12 @@ static PyObject *py_receive_routed(PyObject *m, PyObject *args)
     size_t *ol = (size_t *)malloc((2 * (size_t)n + 1) * sizeof(size_t));
     PyObject *ret = NULL, *route = NULL, *recs = NULL, *deferred = NULL, *sexp_out = NULL, *closed_out = NULL;
     PyObject *empty = NULL, *minus1 = NULL, *zero = NULL, *s_key = NULL, *s_dec = NULL, *s_rsv = NULL, *s_closed = NULL;
-    PyObject *walked = NULL;
-    if (!offs || !cexp || !lens || !cslot || !conn_of || !slot_of || !dg || !desc || !res || !cd || !cs || !cl ||
+    PyObject *walked = NULL, *longs = NULL;
+    if (!offs || !cexp || !lens || !cslot || !conn_of || !slot_of || !dg || !lidx || !cd || !cs || !cl ||
         !blocked_pair || !blocked_space || !blocked_conn || !od || !os_ || !ol)
         goto nomem;
     size_t total = 0;
+    uint32_t nl = 0;  /* datagrams whose first byte says long header: the device walks them */
     for (Py_ssize_t i = 0; i < n; ++i) {
         PyObject *d = PyTuple_GetItem(dgs, i);
         if (!d || !PyBytes_Check(d)) {
@@ -2196,7 +2432,15 @@ static PyObject *py_receive_routed(PyObject *m, PyObject *args)
         cs[i] = (const uint8_t *)PyBytes_AsString(d);
         cl[i] = (size_t)len;
         total += (size_t)len;
+        if (walk && can_walk && len && (cs[i][0] & 0x80)) lidx[nl++] = (uint32_t)i;
     }
+    if ((uint64_t)n + 3ull * nl > 0x7fffffffull) nl = 0;  /* past the fused call's limit: the general path */
+    const size_t nd = (size_t)n + 3 * (size_t)nl, nd1 = nd ? nd : 1, nl1 = nl ? nl : 1;
+    desc = (qpp_desc *)malloc(nd1 * sizeof(qpp_desc));
+    res = (qpp_result *)malloc(nd1 * sizeof(qpp_result));
+    wrec = (qpp_walk_rec *)calloc(nl1 * QPP_WALK_MAX, sizeof(qpp_walk_rec));
+    wn = (uint32_t *)calloc(nl1, sizeof(uint32_t));
+    if (!desc || !res || !wrec || !wn) goto nomem;
     for (Py_ssize_t c = 0; c < nc; ++c) {
         cslot[c] = ((const uint8_t *)a_closed)[c] ? QPP_SLOT_NONE : pslot[cpair[c]];
         cexp[c] = ((const uint64_t *)a_sexp)[cspace[c]];
@@ -2207,13 +2451,18 @@ static PyObject *py_receive_routed(PyObject *m, PyObject *args)
     uint8_t *hin = NULL, *hout = NULL;
     if (n) {
         qpp_session *ss = session();
-        if (!ss || check_rc(qpp_session_stage(ss, total ? total : 1, (uint32_t)n, &hin, &hout)) < 0) goto done;
+        if (!ss || check_rc(qpp_session_stage(ss, total ? total : 1, (uint32_t)nd, &hin, &hout)) < 0) goto done;
         for (Py_ssize_t i = 0; i < n; ++i) cd[i] = hin + offs[i];
         int rc;
         Py_BEGIN_ALLOW_THREADS  /* the snapshot holds every datagram */
         par_copy(cd, cs, cl, (size_t)n, total);
-        rc = qpp_session_route_unprotect(ss, kt, map, cid_len, offs, lens, (uint32_t)n, hin, total, cslot, cexp,
-                                         (uint32_t)nc, 0, hout, total, desc, (qpp_route_rec *)rr, res);
+        if (nl)
+            rc = qpp_session_route_walk_unprotect(ss, kt, map, cid_len, offs, lens, (uint32_t)n, hin, total, lidx, nl,
+                                                  (const uint32_t *)a_kslot, (const uint64_t *)a_kexp, (uint32_t)nc,
+                                                  0, hout, total, desc, (qpp_route_rec *)rr, res, wrec, wn);
+        else
+            rc = qpp_session_route_unprotect(ss, kt, map, cid_len, offs, lens, (uint32_t)n, hin, total, cslot, cexp,
+                                             (uint32_t)nc, 0, hout, total, desc, (qpp_route_rec *)rr, res);
         Py_END_ALLOW_THREADS
         if (check_rc(rc) < 0) goto done;
     }
@@ -2229,7 +2478,22 @@ static PyObject *py_receive_routed(PyObject *m, PyObject *args)
         ++nr;
     }
     if (!walk) {
-        ret = PyTuple_Pack(2, route, Py_None);
+        /* long headers of known connections: with the device's walk of them
+           (walk records, every descriptor and result, the output), or for
+           the caller's general path */
+        if (nl) {
+            PyObject *f[6] = {PyBytes_FromStringAndSize((const char *)lidx, (Py_ssize_t)nl * 4),
+                              PyBytes_FromStringAndSize((const char *)wrec,
+                                                        (Py_ssize_t)nl * QPP_WALK_MAX * (Py_ssize_t)sizeof(qpp_walk_rec)),
+                              PyBytes_FromStringAndSize((const char *)wn, (Py_ssize_t)nl * 4),
+                              PyBytes_FromStringAndSize((const char *)desc, (Py_ssize_t)(nd * sizeof(qpp_desc))),
+                              PyBytes_FromStringAndSize((const char *)res, (Py_ssize_t)(nd * sizeof(qpp_result))),
+                              PyBytes_FromStringAndSize((const char *)hout, (Py_ssize_t)total)};
+            if (f[0] && f[1] && f[2] && f[3] && f[4] && f[5]) longs = PyTuple_Pack(6, f[0], f[1], f[2], f[3], f[4], f[5]);
+            for (int k = 0; k < 6; ++k) Py_XDECREF(f[k]);
+            if (!longs) goto done;
+        }
+        ret = PyTuple_Pack(3, route, Py_None, longs ? longs : Py_None);
         goto done;
     }
     sexp_out = PyBytes_FromStringAndSize(a_sexp, l_sexp);
@@ -2257,12 +2521,14 @@ static PyObject *py_receive_routed(PyObject *m, PyObject *args)
         Py_END_ALLOW_THREADS
     }
     walked = PyTuple_Pack(4, recs, deferred, sexp_out, closed_out);
-    if (walked) ret = PyTuple_Pack(2, route, walked);
+    if (walked) ret = PyTuple_Pack(3, route, walked, Py_None);
     goto done;
 nomem:
     PyErr_NoMemory();
 done:
     free(offs), free(cexp), free(lens), free(cslot), free(conn_of), free(slot_of), free(dg), free(desc), free(res);
+    free(lidx), free(wrec), free(wn);
+    Py_XDECREF(longs);
     free(cd), free(cs), free(cl), free(blocked_pair), free(blocked_space), free(blocked_conn), free(od), free(os_);
     free(ol);
     Py_DECREF(dgs);
@@ -2280,6 +2546,36 @@ done:
     Py_XDECREF(s_rsv);
     Py_XDECREF(s_closed);
     return ret;
+}
+
+/* long_dcids(datagrams) -> None when no bytes object of the list starts with
+ * a long header (first byte, bit 7), else the set of the destination CIDs of
+ * those that do and carry one whole (flags, version, DCID length <= 20, DCID:
+ * what qpp_route classes QPP_R_LONG).  Other items count as none. */
+static PyObject *py_long_dcids(PyObject *m, PyObject *args)
+{
+    PyObject *dgs;
+    if (!PyArg_ParseTuple(args, "O!", &PyList_Type, &dgs)) return NULL;
+    const Py_ssize_t n = PyList_Size(dgs);
+    PyObject *set = NULL;
+    for (Py_ssize_t i = 0; i < n; ++i) {
+        PyObject *d = PyList_GetItem(dgs, i);
+        if (!d || !PyBytes_Check(d)) continue;
+        const Py_ssize_t len = PyBytes_Size(d);
+        const uint8_t *p = (const uint8_t *)PyBytes_AsString(d);
+        if (len < 1 || !(p[0] & 0x80)) continue;
+        if (!set && !(set = PySet_New(NULL))) return NULL;
+        if (len < 6 || p[5] > QPP_CID_MAX || len < 6 + (Py_ssize_t)p[5]) continue;
+        PyObject *cid = PyBytes_FromStringAndSize((const char *)p + 6, p[5]);
+        if (!cid || PySet_Add(set, cid) < 0) {
+            Py_XDECREF(cid);
+            Py_DECREF(set);
+            return NULL;
+        }
+        Py_DECREF(cid);
+    }
+    if (set) return set;
+    Py_RETURN_NONE;
 }
 
 static PyObject *py_hp_mask_host(PyObject *m, PyObject *args)
@@ -2353,6 +2649,13 @@ static PyObject *py_decode_pn_signed(PyObject *m, PyObject *args)
 }
 
 static PyMethodDef module_methods[] = {
+    {"route_walk", py_route_walk, METH_VARARGS, "qpp_route_walk on device buffers"},
+    {"route_walk_unprotect_host", py_route_walk_unprotect_host, METH_VARARGS,
+     "qpp_session_route_walk_unprotect on host buffers"},
+    {"route_walk_launches", py_route_walk_launches, METH_NOARGS, "qpp_route_walk_launches()"},
+    {"long_dcids", py_long_dcids, METH_VARARGS,
+     "long_dcids(datagrams) -> None, or the set of the DCIDs of the datagrams that start with a long header"},
+    {"walk_results", py_walk_results, METH_VARARGS, "unprotect_walk's walk over the results of a launch that has run"},
     {"protect", py_protect, METH_VARARGS, "protect(table, desc_ptr, n, in_ptr, out_ptr, res_ptr, stream, plan=None)"},
     {"unprotect", py_unprotect, METH_VARARGS, "unprotect(table, desc_ptr, n, in_ptr, out_ptr, res_ptr, stream, plan=None)"},
     {"plan_build", py_plan_build, METH_VARARGS, "plan_build(plan, table, desc_ptr, n, stream)"},
@@ -2380,7 +2683,8 @@ static PyMethodDef module_methods[] = {
      "out_len) -> (out, desc, route, results)"},
     {"receive_routed", py_receive_routed, METH_VARARGS,
      "receive_routed(table, map, cid_len, datagrams, conn_pair_u32, conn_space_u32, pair_slot_u32, space_exp_u64, "
-     "rec_type, packet_type, epoch, conn_closed_u8, walk) -> (route, None | (records, deferred, space_exp, closed))"},
+     "conn_keyset_slot_u32, conn_space_exp_u64, rec_type, packet_type, epoch, conn_closed_u8, walk) -> "
+     "(route, None | (records, deferred, space_exp, closed), None | (long_idx, walk, walk_n, desc, results, out))"},
     {"hp_mask_host", py_hp_mask_host, METH_VARARGS, "hp_mask_host(table, slots_u32, samples) -> masks"},
     {"device_ok", py_device_ok, METH_NOARGS, "True when a gfx950 device is usable"},
     {"abi_version", py_abi, METH_NOARGS, "C ABI version of libquicpp"},

@@ -1,5 +1,6 @@
 // qpp_route.hip -- routing received datagrams to connections by connection ID
-// on the device (quic_pp.h: qpp_cidmap_*, qpp_route, qpp_session_route_unprotect).
+// on the device (quic_pp.h: qpp_cidmap_*, qpp_route, qpp_route_walk,
+// qpp_session_route_unprotect, qpp_session_route_walk_unprotect).
 //
 // Replaces the per-datagram routing of the reference's server
 // (asyncio/server.py:60-152: pull_quic_header, then
@@ -10,6 +11,7 @@
 // mirror and then scatter only the buckets they changed to the device copy.
 // k_route only reads the table: no device-side inserts, no atomics.
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <new>
 #include <stdlib.h>
 #include <string.h>
@@ -17,6 +19,7 @@
 #include "quic_pp.h"
 #include "qpp_internal.h"
 #include "qpp_route.h"
+#include "qpp_walk.h"
 
 using qpp_rt::Bucket;
 using qpp_rt::HostMap;
@@ -25,6 +28,11 @@ static_assert(sizeof(qpp_cid_entry) == 32 && sizeof(qpp_route_rec) == 8 && sizeo
 static_assert(QPP_R_SHORT == qpp_rt::kShort && QPP_R_LONG == qpp_rt::kLong &&
               QPP_R_UNKNOWN_CID == qpp_rt::kUnknownCid && QPP_R_MALFORMED == qpp_rt::kMalformed &&
               QPP_R_BAD_CONN == qpp_rt::kBadConn && QPP_CONN_NONE == qpp_rt::kConnNone, "route classes");
+static_assert(sizeof(qpp_walk_rec) == sizeof(qpp_wk::Rec) && QPP_WALK_MAX == qpp_wk::kWalkMax &&
+              QPP_KEYSETS == qpp_wk::kKeysets && QPP_SPACES == qpp_wk::kSpaces &&
+              QPP_DESC_NONE == qpp_wk::kDescNone && QPP_MAX_HDR == qpp_wk::kMaxHdr &&
+              QPP_W_OK == qpp_wk::kOk && QPP_W_PARSE == qpp_wk::kParse && QPP_W_HOST == qpp_wk::kHost,
+              "walk records");
 
 struct qpp_cidmap {
     HostMap host;
@@ -119,6 +127,97 @@ __global__ __launch_bounds__(kRouteWG) void k_route(const Bucket *tab, uint32_t 
     r.rsv[0] = r.rsv[1] = r.rsv[2] = 0;
     route[i] = r;
 }
+
+// One lane per listed long-header datagram (k_walk): the serial
+// walk of qpp_walk.h over the lane's own datagram, byte loads only, each record
+// and descriptor stored as it is found.  No LDS, no atomics: where everything
+// goes is fixed by (n, r, k).
+__global__ __launch_bounds__(kRouteWG) void k_walk(uint32_t cid_len, const uint64_t *off, const uint32_t *len,
+                                                   uint32_t n, const uint8_t *in, const qpp_route_rec *route,
+                                                   const uint32_t *long_idx, uint32_t n_long,
+                                                   const uint32_t *conn_slot, const uint64_t *conn_expected,
+                                                   uint32_t n_conn, uint32_t flags, qpp_desc *desc,
+                                                   qpp_walk_rec *walk, uint32_t *walk_n)
+{
+    const uint32_t r = blockIdx.x * kRouteWG + threadIdx.x;
+    if (r >= n_long) return;
+    const uint32_t i = long_idx[r];
+    const uint32_t extra = n + 3u * r;  // descriptors of packets 1..3
+    qpp_walk_rec none;
+    none.off = none.len = none.version = none.desc = 0;
+    none.pn_off = none.token_len = 0;
+    none.type = none.status = none.dcid_len = none.scid_len = 0;
+    if (i >= n) {
+        // not the caller's contract: nothing of the batch is this lane's, and
+        // its extra descriptors are inert all the same
+        qpp_desc d;
+        d.in_off = 0;
+        d.out_off = 0;
+        d.len = 0;
+        d.hdr_len = 0;
+        d.flags = (uint16_t)flags;
+        d.pn = 0;
+        d.slot = QPP_SLOT_NONE;
+        d.rsv = 0;
+        for (uint32_t k = 0; k < QPP_WALK_MAX - 1; ++k) desc[extra + k] = d;
+        for (uint32_t k = 0; k < QPP_WALK_MAX; ++k) walk[(size_t)r * QPP_WALK_MAX + k] = none;
+        walk_n[r] = 0;
+        return;
+    }
+    const uint64_t o = off[i];
+    const uint32_t l = len[i];
+    const uint8_t *p = in + o;
+    const qpp_route_rec rr = route[i];
+    // a class that passed classify()'s long-header checks: byte 0 is there
+    const bool is_long = rr.cls == QPP_R_LONG || (rr.cls == QPP_R_BAD_CONN && l > 0 && (p[0] & 0x80));
+    const bool keyed = rr.cls == QPP_R_LONG && rr.conn < n_conn;
+    qpp_desc inert;
+    inert.in_off = o;
+    inert.out_off = o;
+    inert.len = 0;
+    inert.hdr_len = 0;
+    inert.flags = (uint16_t)flags;
+    inert.pn = 0;
+    inert.slot = QPP_SLOT_NONE;
+    inert.rsv = 0;
+    uint32_t found = 0;
+    if (is_long) {
+        found = qpp_wk::walk(p, l, cid_len, [&](uint32_t k, qpp_wk::Rec &w) {
+            const uint32_t at = k == 0 ? i : extra + k - 1;
+            if (keyed && w.status == QPP_W_OK && qpp_wk::protected_type(w.type)) {
+                const uint32_t ks = qpp_wk::keyset_of(w.type, w.version);
+                qpp_desc d = inert;
+                d.in_off = o + w.off;
+                d.out_off = o + w.off;
+                d.len = w.len;
+                d.hdr_len = w.pn_off;
+                d.pn = conn_expected[(size_t)rr.conn * QPP_SPACES + qpp_wk::space_of(w.type)];
+                d.slot = ks == qpp_wk::kKeysetNone ? QPP_SLOT_NONE : conn_slot[(size_t)rr.conn * QPP_KEYSETS + ks];
+                desc[at] = d;
+                w.desc = at;
+            } else if (k) {
+                desc[at] = inert;
+            }
+            qpp_walk_rec q;
+            q.off = w.off;
+            q.len = w.len;
+            q.version = w.version;
+            q.desc = w.desc;
+            q.pn_off = w.pn_off;
+            q.token_len = w.token_len;
+            q.type = w.type;
+            q.status = w.status;
+            q.dcid_len = w.dcid_len;
+            q.scid_len = w.scid_len;
+            walk[(size_t)r * QPP_WALK_MAX + k] = q;
+        });
+    }
+    for (uint32_t k = found ? found : 1; k < QPP_WALK_MAX; ++k) desc[extra + k - 1] = inert;
+    for (uint32_t k = found; k < QPP_WALK_MAX; ++k) walk[(size_t)r * QPP_WALK_MAX + k] = none;
+    walk_n[r] = found;
+}
+
+std::atomic<uint64_t> g_walk_launches{0};
 
 void map_entries(const qpp_cid_entry *e, uint32_t n, std::vector<HostMap::Entry> &v)
 {
@@ -266,37 +365,87 @@ int qpp_route(const qpp_cidmap *m, uint32_t cid_len, const uint64_t *d_off, cons
     return QPP_OK;
 }
 
+int qpp_route_walk(uint32_t cid_len, const uint64_t *d_off, const uint32_t *d_len, uint32_t n, const uint8_t *d_in,
+                   const qpp_route_rec *d_route, const uint32_t *d_long_idx, uint32_t n_long,
+                   const uint32_t *d_conn_slot, const uint64_t *d_conn_expected, uint32_t n_conn,
+                   uint16_t desc_flags, qpp_desc *d_desc, qpp_walk_rec *d_walk, uint32_t *d_walk_n, void *stream)
+{
+    if (cid_len < 1 || cid_len > QPP_CID_MAX) return QPP_E_ARG;
+    if (n_long == 0) return QPP_OK;
+    if (n == 0 || n_long > n || (uint64_t)n + 3ull * n_long > 0x7fffffffull) return QPP_E_ARG;
+    if (!d_off || !d_len || !d_in || !d_route || !d_long_idx || !d_desc || !d_walk || !d_walk_n ||
+        (n_conn && (!d_conn_slot || !d_conn_expected)))
+        return QPP_E_ARG;
+    hipLaunchKernelGGL(k_walk, dim3((n_long + kRouteWG - 1) / kRouteWG), dim3(kRouteWG), 0, (hipStream_t)stream,
+                       cid_len, d_off, d_len, n, d_in, d_route, d_long_idx, n_long, d_conn_slot, d_conn_expected,
+                       n_conn, (uint32_t)desc_flags, d_desc, d_walk, d_walk_n);
+    HIPCHK(hipGetLastError());
+    g_walk_launches.fetch_add(1, std::memory_order_relaxed);
+    return QPP_OK;
+}
+
+uint64_t qpp_route_walk_launches(void) { return g_walk_launches.load(std::memory_order_relaxed); }
+
+// Both session forms.  walk_form: conn_slot / conn_expected are the walk's
+// per-key-set and per-space arrays, and the routing kernel's per-connection
+// ones (the 1-RTT slot, the application space's number) are taken from them.
 static int route_unprotect(qpp_session *s, const qpp_keytab *kt, const qpp_cidmap *m, uint32_t cid_len,
                            const uint64_t *off, const uint32_t *len, uint32_t n, const uint8_t *in, size_t in_len,
-                           const uint32_t *conn_slot, const uint64_t *conn_expected, uint32_t n_conn,
-                           uint16_t desc_flags, uint8_t *out, size_t out_len, qpp_desc *desc_out,
-                           qpp_route_rec *route_out, qpp_result *res)
+                           bool walk_form, const uint32_t *long_idx, uint32_t n_long, const uint32_t *conn_slot,
+                           const uint64_t *conn_expected, uint32_t n_conn, uint16_t desc_flags, uint8_t *out,
+                           size_t out_len, qpp_desc *desc_out, qpp_route_rec *route_out, qpp_result *res,
+                           qpp_walk_rec *walk_out, uint32_t *walk_n_out)
 {
     if (!s || !kt || !m || cid_len < 1 || cid_len > QPP_CID_MAX) return QPP_E_ARG;
-    if (n == 0) return QPP_OK;
+    if (n == 0) return n_long ? QPP_E_ARG : QPP_OK;
     if (!off || !len || !route_out || !res || (in_len && !in) || (out_len && !out) ||
         (n_conn && (!conn_slot || !conn_expected)))
+        return QPP_E_ARG;
+    if (n_long && (!long_idx || !walk_out || !walk_n_out || n_long > n || (uint64_t)n + 3ull * n_long > 0x7fffffffull))
         return QPP_E_ARG;
     // the caller's own arrays: every datagram inside both buffers, or nothing runs
     for (uint32_t i = 0; i < n; ++i)
         if (off[i] > in_len || len[i] > in_len - off[i] || off[i] > out_len || len[i] > out_len - off[i])
             return QPP_E_ARG;
-    // scratch: [off | len | conn_slot | conn_expected] go up in one copy,
-    // [desc | route | results] come back in one
+    for (uint32_t r = 0; r < n_long; ++r)
+        if (long_idx[r] >= n || (r && long_idx[r] <= long_idx[r - 1])) return QPP_E_ARG;
+    const uint32_t nd = n + 3u * n_long;  // descriptors and results
+    // scratch: [off | len | conn_slot | conn_expected | long_idx | key-set slots | space numbers]
+    // go up in one copy, [desc | route | results | walk records | walk counts] come back in one
     const size_t o_len = al256((size_t)n * 8), o_slot = o_len + al256((size_t)n * 4),
-                 o_exp = o_slot + al256((size_t)n_conn * 4), up = o_exp + al256((size_t)n_conn * 8);
-    const size_t o_route = al256((size_t)n * sizeof(qpp_desc)), o_res = o_route + al256((size_t)n * sizeof(qpp_route_rec)),
-                 down = o_res + al256((size_t)n * sizeof(qpp_result));
+                 o_exp = o_slot + al256((size_t)n_conn * 4), o_long = o_exp + al256((size_t)n_conn * 8),
+                 o_kslot = o_long + (n_long ? al256((size_t)n_long * 4) : 0),
+                 o_kexp = o_kslot + (n_long ? al256((size_t)n_conn * QPP_KEYSETS * 4) : 0),
+                 up = o_kexp + (n_long ? al256((size_t)n_conn * QPP_SPACES * 8) : 0);
+    const size_t o_route = al256((size_t)nd * sizeof(qpp_desc)),
+                 o_res = o_route + al256((size_t)n * sizeof(qpp_route_rec)),
+                 o_walk = o_res + al256((size_t)nd * sizeof(qpp_result)),
+                 o_walkn = o_walk + (n_long ? al256((size_t)n_long * QPP_WALK_MAX * sizeof(qpp_walk_rec)) : 0),
+                 down = o_walkn + (n_long ? al256((size_t)n_long * 4) : 0);
     qpp_session_bufs b;
     const size_t need = in_len > out_len ? in_len : out_len;
-    int rc = qpp_internal_session_bufs(s, need, n, up + down, &b);
+    int rc = qpp_internal_session_bufs(s, need, nd, up + down, &b);
     if (rc != QPP_OK) return rc;
     uint8_t *hu = b.h_scratch, *du = b.d_scratch, *hd = b.h_scratch + up, *dd = b.d_scratch + up;
     memcpy(hu, off, (size_t)n * 8);
     memcpy(hu + o_len, len, (size_t)n * 4);
-    if (n_conn) {
+    if (n_conn && !walk_form) {
         memcpy(hu + o_slot, conn_slot, (size_t)n_conn * 4);
         memcpy(hu + o_exp, conn_expected, (size_t)n_conn * 8);
+    } else if (n_conn) {
+        uint32_t *sl = (uint32_t *)(hu + o_slot);
+        uint64_t *ex = (uint64_t *)(hu + o_exp);
+        for (uint32_t c = 0; c < n_conn; ++c) {
+            sl[c] = conn_slot[(size_t)c * QPP_KEYSETS + QPP_KEYSETS - 1];
+            ex[c] = conn_expected[(size_t)c * QPP_SPACES + QPP_SPACES - 1];
+        }
+    }
+    if (n_long) {
+        memcpy(hu + o_long, long_idx, (size_t)n_long * 4);
+        if (n_conn) {
+            memcpy(hu + o_kslot, conn_slot, (size_t)n_conn * QPP_KEYSETS * 4);
+            memcpy(hu + o_kexp, conn_expected, (size_t)n_conn * QPP_SPACES * 8);
+        }
     }
     if (in_len && in != b.h_in) memcpy(b.h_in, in, in_len);  // staged by the caller already?
     HIPCHK(hipMemcpyAsync(du, hu, up, hipMemcpyHostToDevice, b.stream));
@@ -310,16 +459,37 @@ static int route_unprotect(qpp_session *s, const qpp_keytab *kt, const qpp_cidma
                    (const uint32_t *)(du + o_slot), (const uint64_t *)(du + o_exp), n_conn, desc_flags, d_desc,
                    d_route, b.stream);
     if (rc != QPP_OK) return rc;
-    rc = qpp_unprotect(kt, d_desc, n, b.d_in, b.d_out, d_res, b.stream);
+    if (n_long) {
+        rc = qpp_route_walk(cid_len, (const uint64_t *)du, (const uint32_t *)(du + o_len), n, b.d_in, d_route,
+                            (const uint32_t *)(du + o_long), n_long, (const uint32_t *)(du + o_kslot),
+                            (const uint64_t *)(du + o_kexp), n_conn, desc_flags, d_desc,
+                            (qpp_walk_rec *)(dd + o_walk), (uint32_t *)(dd + o_walkn), b.stream);
+        if (rc != QPP_OK) return rc;
+    }
+    rc = qpp_unprotect(kt, d_desc, nd, b.d_in, b.d_out, d_res, b.stream);
     if (rc != QPP_OK) return rc;
     if (out_len) HIPCHK(hipMemcpyAsync(b.h_out, b.d_out, out_len, hipMemcpyDeviceToHost, b.stream));
     HIPCHK(hipMemcpyAsync(hd, dd, down, hipMemcpyDeviceToHost, b.stream));
     HIPCHK(hipStreamSynchronize(b.stream));
     if (out_len && out != b.h_out) memcpy(out, b.h_out, out_len);
-    if (desc_out) memcpy(desc_out, hd, (size_t)n * sizeof(qpp_desc));
+    if (desc_out) memcpy(desc_out, hd, (size_t)nd * sizeof(qpp_desc));
     memcpy(route_out, hd + o_route, (size_t)n * sizeof(qpp_route_rec));
-    memcpy(res, hd + o_res, (size_t)n * sizeof(qpp_result));
+    memcpy(res, hd + o_res, (size_t)nd * sizeof(qpp_result));
+    if (n_long) {
+        memcpy(walk_out, hd + o_walk, (size_t)n_long * QPP_WALK_MAX * sizeof(qpp_walk_rec));
+        memcpy(walk_n_out, hd + o_walkn, (size_t)n_long * 4);
+    }
     return QPP_OK;
+}
+
+// no copy into the staging may still be in flight when it is reused
+static int settle(qpp_session *s, int rc)
+{
+    if (rc != QPP_OK && rc != QPP_E_ARG && s) {
+        (void)hipStreamSynchronize((hipStream_t)qpp_session_stream(s));
+        (void)hipGetLastError();
+    }
+    return rc;
 }
 
 int qpp_session_route_unprotect(qpp_session *s, const qpp_keytab *kt, const qpp_cidmap *m, uint32_t cid_len,
@@ -328,14 +498,22 @@ int qpp_session_route_unprotect(qpp_session *s, const qpp_keytab *kt, const qpp_
                                 uint32_t n_conn, uint16_t desc_flags, uint8_t *out, size_t out_len,
                                 qpp_desc *desc_out, qpp_route_rec *route_out, qpp_result *res)
 {
-    const int rc = route_unprotect(s, kt, m, cid_len, off, len, n, in, in_len, conn_slot, conn_expected, n_conn,
-                                   desc_flags, out, out_len, desc_out, route_out, res);
-    if (rc != QPP_OK && rc != QPP_E_ARG && s) {
-        // no copy into the staging may still be in flight when it is reused
-        (void)hipStreamSynchronize((hipStream_t)qpp_session_stream(s));
-        (void)hipGetLastError();
-    }
-    return rc;
+    return settle(s, route_unprotect(s, kt, m, cid_len, off, len, n, in, in_len, false, NULL, 0, conn_slot,
+                                     conn_expected, n_conn, desc_flags, out, out_len, desc_out, route_out, res, NULL,
+                                     NULL));
+}
+
+int qpp_session_route_walk_unprotect(qpp_session *s, const qpp_keytab *kt, const qpp_cidmap *m, uint32_t cid_len,
+                                     const uint64_t *off, const uint32_t *len, uint32_t n, const uint8_t *in,
+                                     size_t in_len, const uint32_t *long_idx, uint32_t n_long,
+                                     const uint32_t *conn_slot, const uint64_t *conn_expected, uint32_t n_conn,
+                                     uint16_t desc_flags, uint8_t *out, size_t out_len, qpp_desc *desc_out,
+                                     qpp_route_rec *route_out, qpp_result *res, qpp_walk_rec *walk_out,
+                                     uint32_t *walk_n_out)
+{
+    return settle(s, route_unprotect(s, kt, m, cid_len, off, len, n, in, in_len, true, long_idx, n_long, conn_slot,
+                                     conn_expected, n_conn, desc_flags, out, out_len, desc_out, route_out, res,
+                                     walk_out, walk_n_out));
 }
 
 }  // extern "C"

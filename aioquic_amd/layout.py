@@ -84,7 +84,16 @@ CID_ENTRY = np.dtype(
 ROUTE = np.dtype([("conn", "<u4"), ("cls", "u1"), ("rsv", "u1", (3,))])
 CONN_NONE = 0xFFFFFFFF
 R_SHORT, R_LONG, R_UNKNOWN_CID, R_MALFORMED, R_BAD_CONN = 0, 1, 2, 3, 4
+# qpp_walk_rec: one packet of a long-header datagram as qpp_route_walk found it
+WALK = np.dtype([("off", "<u4"), ("len", "<u4"), ("version", "<u4"), ("desc", "<u4"), ("pn_off", "<u2"),
+                 ("token_len", "<u2"), ("type", "u1"), ("status", "u1"), ("dcid_len", "u1"), ("scid_len", "u1")])
+WALK_MAX = 4   # QPP_WALK_MAX: packets walked per datagram
+KEYSETS = 5    # QPP_KEYSETS: Initial v1, Initial v2, 0-RTT, Handshake, 1-RTT
+SPACES = 3     # QPP_SPACES: Initial, Handshake, application
+DESC_NONE = 0xFFFFFFFF
+W_OK, W_PARSE, W_HOST = 0, 1, 2
 assert DESC.itemsize == 40 and RESULT.itemsize == 16 and KEY_MATERIAL.itemsize == 84
+assert WALK.itemsize == 24
 assert SECRET.itemsize == 80 and INITIAL.itemsize == 32
 assert CID_ENTRY.itemsize == 32 and ROUTE.itemsize == 8
 

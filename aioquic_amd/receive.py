@@ -308,7 +308,12 @@ def receive_datagrams(items: Sequence[Tuple[ConnectionKeys, bytes]],
                 continue
         _walk_long(conn, d, data, out, queued, add)
     flush_run()
-    results = batch.run()
+    return _finish(items, out, queued, batch.run())
+
+
+def _finish(items, out: list, queued: list, results: list) -> list:
+    """The queued packets' records from their ReceiveBatch outcomes, then the
+    closes; `items[d][0]` is datagram d's connection."""
     cut = False
     for (pos, f), res in zip(queued, results):
         out[pos] = _record(f, res)
@@ -342,6 +347,123 @@ def _apply_closes(items, out: list) -> list:
     return new
 
 
+_V1, _V2 = QuicProtocolVersion.VERSION_1, QuicProtocolVersion.VERSION_2
+_TYPE_OF = [QuicPacketType(k) for k in range(6)]  # by qpp_walk_rec.type
+
+
+def _keysets(conn: ConnectionKeys) -> tuple:
+    """The pairs of layout.KEYSETS 0..3 (Initial v1, Initial v2, 0-RTT,
+    Handshake) as pair_and_space picks them; None where there is none."""
+    ci = conn.cryptos_initial or {}
+    dflt = conn.cryptos.get(Epoch.INITIAL)
+    return (ci.get(_V1, dflt), ci.get(_V2, dflt), conn.cryptos.get(Epoch.ZERO_RTT),
+            conn.cryptos.get(Epoch.HANDSHAKE))
+
+
+def _routed_long(conns, datagrams, cid_len: int, idx: list, cls, rconn, longs, slots) -> Optional[list]:
+    """receive_routed for a batch with long headers to known connections,
+    from what the fused call returned (_crypto.receive_routed): the device
+    has parsed every listed datagram (qpp_walk_rec) and unprotected every
+    packet; policy is decided here per packet in the reference's order
+    (_walk_long), and the remaining packets go through ReceiveBatch's
+    in-order walk over the results already there (ReceiveBatch.preset), in
+    datagram order with coalesced packets in order.  Only what that walk
+    defers (key-phase flips, stale expected numbers) is launched again.
+    None, with no state touched: a datagram the device left to the host walk,
+    or an Initial the device had no key-set for; the caller's general path
+    takes the batch."""
+    lidx_b, walk_b, wn_b, desc_b, res_b, out_b = longs
+    row_of = {i: r for r, i in enumerate(np.frombuffer(lidx_b, np.uint32).tolist())}
+    walk = np.frombuffer(walk_b, dtype=L.WALK).reshape(-1, L.WALK_MAX)
+    wn = np.frombuffer(wn_b, np.uint32).tolist()
+    live = np.arange(L.WALK_MAX)[None, :] < np.asarray(wn, np.int64)[:, None]
+    if ((walk["status"] == L.W_HOST) & live).any():
+        return None
+    w_off, w_len, w_ver, w_desc = (walk[f].tolist() for f in ("off", "len", "version", "desc"))
+    w_pn, w_tok, w_type, w_st = (walk[f].tolist() for f in ("pn_off", "token_len", "type", "status"))
+    w_dl, w_sl = walk["dcid_len"].tolist(), walk["scid_len"].tolist()
+    one_rtt, ep1, initial = QuicPacketType.ONE_RTT, Epoch.ONE_RTT, QuicPacketType.INITIAL
+    out: list = []
+    queued: list = []
+    pairs, packets, offs, spaces, pconns, rsvs, dix = [], [], [], [], [], [], []
+    items = {}
+    by_conn: dict = {}
+    r_short = L.R_SHORT
+    for i in idx:
+        conn = conns[rconn[i]]
+        data = datagrams[i]
+        items[i] = (conn, data)
+        if conn.closed:
+            out.append(_closed_record(i))  # connection.py:756-757
+            continue
+        if cls[i] == r_short:
+            c = by_conn.get(id(conn))
+            if c is None:
+                c = by_conn[id(conn)] = conn.pair_and_space(ep1, None)
+            queued.append((len(out), (i, 0, None, one_rtt, ep1)))
+            out.append(None)
+            pairs.append(c[0]), packets.append(data), offs.append(1 + cid_len), spaces.append(c[1])
+            pconns.append(conn), rsvs.append(_RSV_SHORT), dix.append(i)
+            continue
+        r = row_of[i]
+        for k in range(wn[r]):
+            start = w_off[r][k]
+            if w_st[r][k] == L.W_PARSE:
+                out.append(ReceivedPacket(i, start, None, one_rtt, None, dropped="header_parse_error"))
+                break
+            ptype = _TYPE_OF[w_type[r][k]]
+            if ptype in (QuicPacketType.VERSION_NEGOTIATION, QuicPacketType.RETRY):
+                # the device left the version list and the Retry token unread: the host parser's
+                buf = Buffer(data=data)
+                buf.seek(start)
+                try:
+                    header = pull_quic_header(buf, host_cid_length=cid_len)
+                except ValueError:
+                    out.append(ReceivedPacket(i, start, None, one_rtt, None, dropped="header_parse_error"))
+                    break
+            elif ptype == one_rtt:
+                header = QuicHeader(None, one_rtt, w_len[r][k], data[start + 1:start + 1 + cid_len], b"")
+            else:
+                at = start + 6 + w_dl[r][k]
+                dcid, scid = data[start + 6:at], data[at + 1:at + 1 + w_sl[r][k]]
+                token = b""
+                if ptype == initial:
+                    at += 1 + w_sl[r][k]
+                    at += 1 << (data[at] >> 6)  # the token length's own bytes
+                    token = data[at:at + w_tok[r][k]]
+                header = QuicHeader(w_ver[r][k], ptype, w_len[r][k], dcid, scid, token=token)
+            if not conn.is_client and ptype == initial and len(data) < SMALLEST_MAX_DATAGRAM_SIZE:
+                out.append(ReceivedPacket(i, start, header, ptype, Epoch.INITIAL,
+                                          dropped="initial_packet_datagram_too_small"))
+                break
+            if conn.cid_unknown(ptype, header.destination_cid):
+                out.append(ReceivedPacket(i, start, header, ptype, None, dropped="unknown_connection_id"))
+                break
+            if ptype == QuicPacketType.VERSION_NEGOTIATION:
+                out.append(ReceivedPacket(i, start, header, ptype, None))
+                break
+            if header.version is not None and header.version not in conn.supported_versions:
+                out.append(ReceivedPacket(i, start, header, ptype, None, dropped="unsupported_version"))
+                break
+            if ptype == QuicPacketType.RETRY:
+                out.append(ReceivedPacket(i, start, header, ptype, None))
+                break
+            epoch = _EPOCH_OF_TYPE[ptype]
+            pair, space = conn.pair_and_space(epoch, header.version)
+            if ptype == initial and header.version not in (_V1, _V2) and pair is not None \
+                    and pair.recv.aead is not None:
+                return None  # keys the device had no key-set for
+            queued.append((len(out), (i, start, header, ptype, epoch)))
+            out.append(None)
+            pairs.append(pair), packets.append(data[start:start + w_len[r][k]]), offs.append(w_pn[r][k])
+            spaces.append(space), pconns.append(conn)
+            rsvs.append(_RSV_SHORT if ptype == one_rtt else _RSV_LONG), dix.append(w_desc[r][k])
+    rb = ReceiveBatch(slots=slots)
+    rb._extend(pairs, packets, offs, spaces, pconns, rsvs)
+    rb.preset(desc_b, res_b, dix, out_b)
+    return _finish(items, out, queued, rb.run())
+
+
 def receive_routed(router, datagrams: Sequence[bytes]) -> Tuple[List[ReceivedPacket], List[Tuple[int, int]]]:
     """receive_datagrams for raw datagrams nobody has demultiplexed: the
     device routes each to its connection by connection ID (route.CidRouter,
@@ -356,12 +478,23 @@ def receive_routed(router, datagrams: Sequence[bytes]) -> Tuple[List[ReceivedPac
     CID, a long header with an unknown DCID, a malformed datagram -- the
     caller's new-connection, stateless-reset and drop business (:86-152).
 
-    When every routed datagram is a short header, the batch is staged once and
-    one call routes and unprotects it (_crypto.receive_routed).  A long header
-    to a known connection (Handshake traffic to a host CID), or a client that
-    checks its host CIDs, sends the routed datagrams through receive_datagrams
-    instead; their bytes are then uploaded twice, once to route and once to
-    unprotect."""
+    The batch is staged once and one call routes and unprotects it
+    (_crypto.receive_routed).  Long headers to known connections (Handshake
+    traffic to a host CID, coalesced Initial + Handshake + 1-RTT datagrams,
+    0-RTT) are walked on the device in that same call (qpp_route_walk): the
+    walk records give every coalesced packet's offsets and type, policy
+    (too-small Initial datagrams, unknown Handshake DCIDs, Version Negotiation
+    and Retry, unsupported versions) is decided here in the reference's order,
+    and the in-order walk runs over the results of the one launch
+    (_routed_long).  Key slots beyond the 1-RTT ones are assigned only to the
+    connections that the batch's long headers can reach (by their DCIDs).
+    The general path sends the routed datagrams through receive_datagrams
+    instead, their bytes then uploaded twice, once to route and once to
+    unprotect; it is taken for a client that checks its host CIDs, a datagram
+    the device leaves to the host walk (more than layout.WALK_MAX packets, a
+    header past layout.MAX_HDR), a keyed Initial of a supported version that
+    is neither 1 nor 2, and a key table too small for the reached
+    connections' key-sets beside the 1-RTT ones."""
     datagrams = datagrams if isinstance(datagrams, list) else list(datagrams)
     if not datagrams:
         return [], []
@@ -388,23 +521,73 @@ def receive_routed(router, datagrams: Sequence[bytes]) -> Tuple[List[ReceivedPac
     keyed = [k for k, p in enumerate(upairs) if p.recv.aead is not None]
     # one more pair (no key) and space than there are: a retired index points at them
     pslot = np.full(len(upairs) + 1, 0xFFFFFFFF, np.uint32)
-    if keyed:
-        rc = [upairs[k].recv for k in keyed]
-        pslot[keyed] = slots.assign([(c.aead, c.hp, c.key_phase) for c in rc])
+    # the connections that long-header datagrams of this batch can reach: by
+    # the DCID at their start, as qpp_route will find them (None: no long header)
+    dcids = None if general else _crypto.long_dcids(datagrams)
+    touched = None if dcids is None else sorted({c for c in map(router.index_of, dcids) if c is not None})
+    xp: list = []
+    if touched:
+        # their other key-sets that have keys (a connection past its handshake
+        # holds its 1-RTT slot alone)
+        sets = {c: _keysets(conns[c]) for c in touched if not conns[c].closed}
+        extra = {id(p): p for ks in sets.values() for p in ks if p is not None and p.recv.aead is not None}
+        xp = [p for k, p in extra.items() if k not in pix]
+    got: list = []
+    if keyed or xp:
+        # one assign() for the whole batch: a refill must not take an earlier slot away
+        rc = [upairs[k].recv for k in keyed] + [p.recv for p in xp]
+        try:
+            got = slots.assign([(c.aead, c.hp, c.key_phase) for c in rc])
+        except OverflowError:
+            if not xp:
+                raise
+            # the table cannot hold these key-sets beside the 1-RTT ones: the general path
+            dcids, xp = None, []
+            got = slots.assign([(c.aead, c.hp, c.key_phase) for c in rc[:len(keyed)]])
+        pslot[keyed] = got[:len(keyed)]
     sexp = np.asarray([sp.expected_packet_number & 0xFFFFFFFFFFFFFFFF for sp in uspaces] + [0], np.uint64)
     a_pair = np.asarray(c_pair, np.int64)
     a_space = np.asarray(c_space, np.int64)
     a_pair[a_pair < 0] = len(upairs)
     a_space[a_space < 0] = len(uspaces)
-    route_b, walked = _crypto.receive_routed(
+    kslot = kexp = b""
+    if dcids is not None:
+        # the device walk's arrays: a slot per connection and key-set, an
+        # expected number per connection and space; only the connections the
+        # long headers can reach have more than their 1-RTT entries
+        ks_arr = np.full((len(conns), L.KEYSETS), L.SLOT_NONE, np.uint32)
+        ke_arr = np.zeros((len(conns), L.SPACES), np.uint64)
+        if len(conns):
+            ks_arr[:, 4] = pslot[a_pair]
+            ks_arr[np.asarray([k for k, c in enumerate(conns) if c is not None and c.closed], np.int64), 4] = L.SLOT_NONE
+            ke_arr[:, 2] = sexp[a_space]
+        xslot = {id(p): s_ for p, s_ in zip(xp, got[len(keyed):])}
+        xslot.update((id(upairs[k]), int(pslot[k])) for k in keyed)
+        for c in touched:
+            if conns[c].closed:
+                continue
+            for j, p in enumerate(sets[c]):
+                if p is not None:
+                    ks_arr[c, j] = xslot.get(id(p), L.SLOT_NONE)
+            sp = conns[c].spaces
+            for j, e in enumerate((Epoch.INITIAL, Epoch.HANDSHAKE)):
+                if e in sp:
+                    ke_arr[c, j] = sp[e].expected_packet_number & 0xFFFFFFFFFFFFFFFF
+        kslot, kexp = ks_arr.tobytes(), ke_arr.tobytes()
+    route_b, walked, longs = _crypto.receive_routed(
         slots.table, router.map, router.host_cid_length, datagrams, a_pair.astype(np.uint32).tobytes(),
-        a_space.astype(np.uint32).tobytes(), pslot.tobytes(), sexp.tobytes(), ReceivedPacket, QuicPacketType.ONE_RTT,
-        Epoch.ONE_RTT, bytes(bool(c is not None and c.closed) for c in conns), 0 if general else 1)
+        a_space.astype(np.uint32).tobytes(), pslot.tobytes(), sexp.tobytes(), kslot, kexp, ReceivedPacket,
+        QuicPacketType.ONE_RTT, Epoch.ONE_RTT, bytes(bool(c is not None and c.closed) for c in conns),
+        0 if general else 1)
     route = np.frombuffer(route_b, dtype=L.ROUTE)
     cls, rconn = route["cls"], route["conn"]
     routed = ((cls == L.R_SHORT) | (cls == L.R_LONG)) & (rconn != L.CONN_NONE)
     unrouted = [(int(i), int(cls[i])) for i in np.flatnonzero(~routed)]
     idx = np.flatnonzero(routed)
+    if longs is not None:
+        recs = _routed_long(conns, datagrams, router.host_cid_length, idx.tolist(), cls, rconn, longs, slots)
+        if recs is not None:
+            return recs, unrouted
     if walked is None:
         items = [(conns[rconn[i]], datagrams[i]) for i in idx.tolist()]
         back = idx.tolist()

@@ -43,6 +43,10 @@ class CidRouter:
     def __len__(self) -> int:
         return len(self._cids)
 
+    def index_of(self, cid: bytes) -> Optional[int]:
+        """The index `cid` routes to, or None."""
+        return self._cids.get(bytes(cid))
+
     def add(self, cid: bytes, conn) -> int:
         """_connection_id_issued: route `cid` to `conn`; returns its index."""
         if conn.host_cid_length != self.host_cid_length:

@@ -352,7 +352,7 @@ uint32_t qpp_cidmap_buckets(const qpp_cidmap *m);
  * qpp_unprotect, unchanged. */
 #define QPP_R_SHORT 0        /* short header, CID known: the descriptor is ready for qpp_unprotect */
 #define QPP_R_LONG 1         /* long header (bit 7): conn = its DCID's connection or QPP_CONN_NONE;
-                                the packets of the datagram are the host walk's */
+                                the packets of the datagram are qpp_route_walk's, or the host walk's */
 #define QPP_R_UNKNOWN_CID 2  /* short header, CID not in the map */
 #define QPP_R_MALFORMED 3    /* empty; (b0 & 0xC0) == 0; short and len < 1 + cid_len; long and
                                 len < 6, DCID length > 20 or len < 6 + DCID length */
@@ -367,6 +367,78 @@ int qpp_route(const qpp_cidmap *m, uint32_t cid_len, const uint64_t *d_off, cons
               uint32_t n, const uint8_t *d_in, const uint32_t *d_conn_slot,
               const uint64_t *d_conn_expected, uint32_t n_conn, uint16_t desc_flags,
               qpp_desc *d_desc /* may be NULL */, qpp_route_rec *d_route, void *stream);
+
+/* qpp_route_walk: the header walk of the long-header datagrams of a routed
+ * batch on the device, in place of the host's per-datagram pull_quic_header
+ * loop (quic/packet.py:181-267, connection.py:793-899).  Asynchronous on
+ * `stream`; runs after qpp_route on the same stream, over the same datagram
+ * arrays and the d_route (read only here) and d_desc that qpp_route wrote.
+ * d_long_idx[n_long] names the datagrams to walk, strictly increasing and
+ * < n (the caller's to guarantee for this device form; an index >= n is
+ * skipped: no packets, zeroed records, inert extra descriptors).  One lane per listed datagram: lane r walks datagram i =
+ * d_long_idx[r] and writes d_walk_n[r] = its packets found, at most
+ * QPP_WALK_MAX, and one record d_walk[r * QPP_WALK_MAX + k] per packet k
+ * (records past d_walk_n[r] are written as zeros).  A lane reads header bytes of its
+ * datagram only, each after a check against d_len[i]: never a byte at or past
+ * d_len[i], whatever the header's length fields claim.
+ *
+ * The walk of a datagram ends at its end (a short header, which is parsed at
+ * any position but the first, Version Negotiation and Retry run to it), at a
+ * header that does not parse (one QPP_W_PARSE record at that packet's offset,
+ * the host walk's "header_parse_error") and at a QPP_W_HOST record: a header
+ * whose pn_off is above QPP_MAX_HDR, or the fourth packet of a datagram that
+ * holds a fifth.  QPP_W_HOST means "leave this datagram to the host walk".
+ * A Version Negotiation packet is QPP_W_OK whatever follows its CIDs: its list
+ * of versions is the host's to validate (pull_quic_header reads it in 4-byte
+ * units and fails on a remainder; receive_routed records that as
+ * header_parse_error, as the host walk does).
+ *
+ * Descriptors.  A datagram that qpp_route classed QPP_R_LONG with a
+ * connection gets, for each QPP_W_OK packet of type Initial, 0-RTT, Handshake
+ * or 1-RTT, {in_off = out_off = d_off[i] + off, len = the packet's length,
+ * hdr_len = pn_off, flags = desc_flags, pn = d_conn_expected[conn *
+ * QPP_SPACES + space], slot = d_conn_slot[conn * QPP_KEYSETS + key-set], rsv
+ * = 0}, with QPP_SLOT_NONE for an Initial of a version that is neither 1 nor
+ * 2.  Packet 0's descriptor replaces d_desc[i]; packet k >= 1 goes to
+ * d_desc[n + 3 r + k - 1]; the record's desc is that index.  Every extra
+ * entry d_desc[n + 3 r .. n + 3 r + 2] with no packet is written inert, as
+ * qpp_route's are: len 0, QPP_SLOT_NONE, offsets d_off[i].  The placement is
+ * fixed by (n, r, k) alone: no atomics, nothing to read back before the
+ * unprotect launch over all n + 3 n_long descriptors (d_desc and the
+ * results are the caller's to size for as many).  The extras of distant
+ * datagrams share 16-packet items, so the QPP_ITEM_SPAN_MAX rule (Buffers,
+ * above) applies to them: past it a packet reports QPP_S_LENGTH, harmlessly.
+ * Version Negotiation and Retry packets, and every packet of a datagram with
+ * no connection (QPP_CONN_NONE) or classed QPP_R_BAD_CONN, get records with
+ * desc = QPP_DESC_NONE, and the conn arrays are not read for them.  A listed
+ * datagram of any other class (not a long header) gets d_walk_n[r] = 0. */
+#define QPP_WALK_MAX 4
+#define QPP_KEYSETS 5   /* per connection: Initial v1, Initial v2, 0-RTT, Handshake, 1-RTT */
+#define QPP_SPACES 3    /* Initial, Handshake, application (0-RTT and 1-RTT share it) */
+#define QPP_DESC_NONE 0xffffffffu
+#define QPP_W_OK 0      /* parsed; desc says whether a descriptor was written */
+#define QPP_W_PARSE 1   /* header_parse_error here; the datagram ends */
+#define QPP_W_HOST 2    /* more than QPP_WALK_MAX packets, or pn_off > QPP_MAX_HDR */
+typedef struct qpp_walk_rec {
+    uint32_t off;       /* packet start within the datagram */
+    uint32_t len;       /* packet_length */
+    uint32_t version;   /* 0: short header or Version Negotiation */
+    uint32_t desc;      /* index into d_desc / d_res, or QPP_DESC_NONE */
+    uint16_t pn_off;    /* encrypted offset from the packet start; 0 for VN and Retry */
+    uint16_t token_len; /* an Initial's token length */
+    uint8_t type;       /* QuicPacketType value 0..5 */
+    uint8_t status;     /* QPP_W_* */
+    uint8_t dcid_len, scid_len;
+} qpp_walk_rec;         /* 24 bytes */
+int qpp_route_walk(uint32_t cid_len, const uint64_t *d_off, const uint32_t *d_len, uint32_t n,
+                   const uint8_t *d_in, const qpp_route_rec *d_route, const uint32_t *d_long_idx,
+                   uint32_t n_long, const uint32_t *d_conn_slot /* n_conn x QPP_KEYSETS */,
+                   const uint64_t *d_conn_expected /* n_conn x QPP_SPACES */, uint32_t n_conn,
+                   uint16_t desc_flags, qpp_desc *d_desc /* n + 3 n_long */, qpp_walk_rec *d_walk,
+                   uint32_t *d_walk_n, void *stream);
+/* qpp_route_walk launches of the walking kernel (process-wide, since the
+ * library loaded).  Diagnostic: an all-short batch makes none. */
+uint64_t qpp_route_walk_launches(void);
 
 /* Header-protection masks: replaces HeaderProtection_mask (_crypto.c:278-287).
  * d_samples: n x 16 bytes, d_masks: n x 16 bytes (first 5 used). */
@@ -403,6 +475,27 @@ int qpp_session_route_unprotect(qpp_session *s, const qpp_keytab *kt, const qpp_
                                 size_t in_len, const uint32_t *conn_slot, const uint64_t *conn_expected,
                                 uint32_t n_conn, uint16_t desc_flags, uint8_t *out, size_t out_len,
                                 qpp_desc *desc_out, qpp_route_rec *route_out, qpp_result *res);
+/* qpp_session_route_unprotect with the device walk of the long-header
+ * datagrams long_idx[n_long] (qpp_route_walk) between the routing kernel and
+ * the unprotect: one H2D, the routing kernel, the walking kernel when n_long >
+ * 0, one unplanned unprotect over n + 3 n_long descriptors, one D2H that
+ * also returns the walk records (walk_out[n_long * QPP_WALK_MAX],
+ * walk_n_out[n_long]).  desc_out (may be NULL) and res hold n + 3 n_long
+ * entries.  The per-connection arrays are the walk's: conn_slot[n_conn *
+ * QPP_KEYSETS], conn_expected[n_conn * QPP_SPACES]; the routing kernel is
+ * given each connection's 1-RTT slot and application-space number from them.
+ * Checked on the host before anything is launched, besides the offsets as
+ * above: long_idx strictly increasing, every index < n, n + 3 n_long <=
+ * 2^31 - 1, walk_out / walk_n_out given when n_long > 0.  A violation is
+ * QPP_E_ARG and nothing is touched.  With n_long == 0 the call does what
+ * qpp_session_route_unprotect does: the same launches, the same bytes. */
+int qpp_session_route_walk_unprotect(qpp_session *s, const qpp_keytab *kt, const qpp_cidmap *m, uint32_t cid_len,
+                                     const uint64_t *off, const uint32_t *len, uint32_t n, const uint8_t *in,
+                                     size_t in_len, const uint32_t *long_idx, uint32_t n_long,
+                                     const uint32_t *conn_slot, const uint64_t *conn_expected, uint32_t n_conn,
+                                     uint16_t desc_flags, uint8_t *out, size_t out_len, qpp_desc *desc_out,
+                                     qpp_route_rec *route_out, qpp_result *res, qpp_walk_rec *walk_out,
+                                     uint32_t *walk_n_out);
 /* The session's own pinned staging buffers, sized for at least `bytes` of
  * input and of output and n packets; valid until the next call on the
  * session.  A caller that assembles its input straight into *h_in and passes

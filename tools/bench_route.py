@@ -19,6 +19,15 @@ suites) in random arrival order, for n = 1 Mi and 64 Ki.
                                       asyncio/server.py:60-152 without its header
                                       parse) and receive_datagrams of the items
 
+  burst    --burst n (default 65536, 0 = skip) datagrams of a connect burst over
+           the same number of connections, every connection with Initial,
+           Handshake and 1-RTT keys: each connection's first datagram a
+           coalesced Initial + Handshake + 1-RTT of 1200 B, one in 16 of the
+           rest a lone Handshake packet, the rest 1-RTT.  The same two host
+           ways: receive_routed (the device walks the long headers in the one
+           fused call) against a Python routing pass (DCID dict lookup) and
+           receive_datagrams of the items (the header walk in Python).
+
 The ways alternate in one process after --warmup rounds; median, min and max
 of --runs rounds.  Every round starts from the same connection state (expected
 packet numbers reset outside the timings).  The two host ways' records are
@@ -49,11 +58,150 @@ class Space:
     expected_packet_number = 0
 
 
+def connect_burst(n, C, runs, warmup):
+    """The connect-burst mix through both host ways -> (numbers, records equal)."""
+    from aioquic_amd import batch_io
+    from aioquic_amd import receive as R
+    from aioquic_amd.crypto import CryptoPair
+    from aioquic_amd.packet import QuicPacketType, QuicProtocolVersion, encode_long_header_first_byte
+    from aioquic_amd.route import CidRouter
+    from aioquic_amd.tls import CipherSuite, Epoch
+
+    rng = np.random.default_rng(0xB0257)
+    version = int(QuicProtocolVersion.VERSION_1)
+    suites = [(CipherSuite.AES_128_GCM_SHA256, 32), (CipherSuite.AES_256_GCM_SHA384, 48),
+              (CipherSuite.CHACHA20_POLY1305_SHA256, 32)]
+    # the burst addresses every connection with all three of its key-sets: either way needs a
+    # slot for each in one batch, more than the default table of this thread has
+    batch_io._per_thread.slots = batch_io.KeySlots(6 * C)
+    cid = rng.integers(0, 256, (C, 8), dtype=np.uint8)
+    cid[:, :4] = np.arange(C, dtype=">u4").view(np.uint8).reshape(C, 4)  # distinct
+    cids = [cid[c].tobytes() for c in range(C)]
+    scid = bytes(8)
+    send_slots = batch_io.KeySlots(6 * C)
+    srv_init = [CryptoPair() for _ in range(C)]
+    cli_init = [CryptoPair() for _ in range(C)]
+    batch_io.setup_initial_batch(srv_init, cids, False, version)
+    batch_io.setup_initial_batch(cli_init, cids, True, version, slots=send_slots)
+    conns, senders = [], []
+    for c in range(C):
+        cs, slen = suites[c % 3]
+        pairs = {}
+        snd = {Epoch.INITIAL: cli_init[c].send}
+        for epoch, suite, ln in ((Epoch.HANDSHAKE, CipherSuite.AES_128_GCM_SHA256, 32), (Epoch.ONE_RTT, cs, slen)):
+            secret = rng.bytes(ln)
+            pairs[epoch] = CryptoPair()
+            pairs[epoch].recv.setup(cipher_suite=suite, secret=secret, version=version)
+            peer = CryptoPair()
+            peer.send.setup(cipher_suite=suite, secret=secret, version=version)
+            snd[epoch] = peer.send
+        pairs[Epoch.INITIAL] = srv_init[c]
+        conns.append(R.ConnectionKeys(cryptos=pairs, spaces={e: Space() for e in (Epoch.INITIAL, Epoch.HANDSHAKE,
+                                                                                  Epoch.ONE_RTT)},
+                                      cryptos_initial={version: srv_init[c]}, host_cid_length=8))
+        senders.append(snd)
+
+    def long_hdr(ptype, c, pn, rest):
+        out = bytes([encode_long_header_first_byte(version, ptype, 1)]) + version.to_bytes(4, "big")
+        out += bytes([8]) + cids[c] + bytes([8]) + scid
+        if ptype == QuicPacketType.INITIAL:
+            out += b"\x00"
+        return out + (0x4000 | (rest + 2)).to_bytes(2, "big") + pn.to_bytes(2, "big")
+
+    def short_hdr(c, pn):
+        return bytes([0x41]) + cids[c] + pn.to_bytes(2, "big")
+
+    # per connection: the coalesced first datagram, then its share of the rest
+    per = [max(n // C, 1)] * C
+    sb = batch_io.SendBatch(slots=send_slots)
+    shape = []  # per datagram: (connection, packets in it)
+    order = np.repeat(np.arange(C), per)
+    rng.shuffle(order)
+    seen = [0] * C
+    pn = [[0, 0, 0] for _ in range(C)]  # Initial, Handshake, application
+    k_rest = 0
+    for c in order.tolist():
+        first = seen[c] == 0
+        seen[c] += 1
+        if first:
+            hi = long_hdr(QuicPacketType.INITIAL, c, 0, 300 + 16)
+            hh = long_hdr(QuicPacketType.HANDSHAKE, c, 0, 200 + 16)
+            hs = short_hdr(c, 0)
+            sb.add(senders[c][Epoch.INITIAL], hi, rng.bytes(300), 0)
+            sb.add(senders[c][Epoch.HANDSHAKE], hh, rng.bytes(200), 0)
+            sb.add(senders[c][Epoch.ONE_RTT], hs, rng.bytes(1200 - len(hi) - len(hh) - len(hs) - 300 - 200 - 48), 0)
+            pn[c] = [1, 1, 1]
+            shape.append((c, 3))
+            continue
+        k_rest += 1
+        if k_rest % 16 == 0:
+            h = long_hdr(QuicPacketType.HANDSHAKE, c, pn[c][1], 1200 - 27 - 16 + 16)
+            sb.add(senders[c][Epoch.HANDSHAKE], h, rng.bytes(1200 - len(h) - 16), pn[c][1])
+            pn[c][1] += 1
+        else:
+            h = short_hdr(c, pn[c][2])
+            sb.add(senders[c][Epoch.ONE_RTT], h, rng.bytes(1200 - len(h) - 16), pn[c][2])
+            pn[c][2] += 1
+        shape.append((c, 1))
+    wires = sb.flush()
+    datagrams, at = [], 0
+    for c, k in shape:
+        datagrams.append(b"".join(wires[at:at + k]))
+        at += k
+    assert all(len(d) == 1200 for d in datagrams)
+    del wires
+    router = CidRouter(8, C)
+    for c, conn in enumerate(conns):
+        router.add(cids[c], conn)
+    by_cid = {cids[c]: conn for c, conn in enumerate(conns)}
+
+    def reset():
+        for conn in conns:
+            for sp in conn.spaces.values():
+                sp.expected_packet_number = 0
+
+    t_routed, t_dict, t_pass = [], [], []
+    got = want = unrouted = None
+    for r in range(warmup + runs):
+        reset()
+        t0 = time.perf_counter()
+        got, unrouted = R.receive_routed(router, datagrams)
+        t1 = time.perf_counter()
+        reset()
+        t2 = time.perf_counter()
+        items = [(by_cid[d[6:14] if d[0] & 0x80 else d[1:9]], d) for d in datagrams]
+        t3 = time.perf_counter()
+        want = R.receive_datagrams(items)
+        t4 = time.perf_counter()
+        if r >= warmup:
+            t_routed.append((t1 - t0) * 1e3)
+            t_pass.append((t3 - t2) * 1e3)
+            t_dict.append((t4 - t2) * 1e3)
+        if r + 1 < warmup + runs:
+            del got, want, items
+    packets = sum(k for _, k in shape)
+    eq = not unrouted and len(got) == len(want) == packets and all(
+        g == w_ and g.dropped is None for g, w_ in zip(got, want))
+    mr, md = statistics.median(t_routed), statistics.median(t_dict)
+    nd = len(datagrams)
+    return {
+        "datagrams": nd, "packets": packets, "connections": C,
+        "coalesced_datagrams": sum(1 for _, k in shape if k == 3),
+        "lone_handshake_datagrams": sum(1 for d in datagrams if d[0] & 0x80) - sum(1 for _, k in shape if k == 3),
+        "receive_routed": dict(_stats(t_routed), datagrams_per_s=round(nd / (mr * 1e-3))),
+        "dict_pass_plus_receive_datagrams": dict(_stats(t_dict), dict_pass=_stats(t_pass),
+                                                 datagrams_per_s=round(nd / (md * 1e-3))),
+        "dict_way_over_routed": round(md / mr, 3),
+        "same_records": bool(eq),
+    }, bool(eq)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--conns", type=int, default=4096)
     ap.add_argument("--sizes", default="1048576,65536", help="datagrams per batch, device part")
     ap.add_argument("--host-sizes", default="1048576,65536", help="datagrams per batch, host part ('' = skip)")
+    ap.add_argument("--burst", type=int, default=65536, help="datagrams of the connect-burst mix (0 = skip)")
     ap.add_argument("--runs", type=int, default=11)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--timeout", type=int, default=900, help="seconds before the run gives up")
@@ -229,6 +377,9 @@ def main():
             "same_records": bool(eq),
         }
         del datagrams, got, want
+    if a.burst:
+        out["connect_burst"], eq = connect_burst(a.burst, C, a.runs, a.warmup)
+        same = same and eq
     line = json.dumps(out)
     print(line)
     if a.out:
