@@ -9,51 +9,13 @@
 
 #include "../../include/quic_pp.h"
 #include "qpp_gh5.h"
+#include "qpp_te4.h"
 
 namespace qpp {
 
 // ---------------------------------------------------------------- tables --
 
-// AES S-box and the little-endian round table Te0 (byte r of a word = row r):
-// Te0[x] = 2S(x) | S(x)<<8 | S(x)<<16 | 3S(x)<<24.  Generated at compile time
-// from GF(2^8) arithmetic (FIPS-197 sec. 5.1.1), so no table is transcribed.
-struct AesTables {
-    uint8_t sbox[256];
-    uint32_t te0[256];
-};
-
-constexpr uint8_t gf8_mul(uint8_t a, uint8_t b)
-{
-    uint8_t r = 0;
-    for (int i = 0; i < 8; ++i) {
-        if (b & 1) r ^= a;
-        a = (uint8_t)((a << 1) ^ ((a & 0x80) ? 0x1b : 0));
-        b >>= 1;
-    }
-    return r;
-}
-
-constexpr AesTables make_aes_tables()
-{
-    AesTables t{};
-    for (int x = 0; x < 256; ++x) {
-        // inverse = x^254 in GF(2^8) (0 maps to 0)
-        uint8_t inv = 1, base = (uint8_t)x;
-        for (int e = 254; e; e >>= 1) {
-            if (e & 1) inv = gf8_mul(inv, base);
-            base = gf8_mul(base, base);
-        }
-        uint8_t s = inv;
-        for (int i = 1; i <= 4; ++i) s ^= (uint8_t)((inv << i) | (inv >> (8 - i)));
-        s ^= 0x63;
-        t.sbox[x] = s;
-        t.te0[x] = (uint32_t)gf8_mul(s, 2) | (uint32_t)s << 8 | (uint32_t)s << 16 |
-                   (uint32_t)gf8_mul(s, 3) << 24;
-    }
-    return t;
-}
-
-constexpr AesTables kAesTables = make_aes_tables();
+// AES S-box and round table Te0, generated at compile time (qpp_te4.h)
 extern __constant__ AesTables c_aes;
 
 // -------------------------------------------------------------- key slots --
@@ -265,10 +227,10 @@ __device__ __forceinline__ u32x4 quad_xor_all(u32x4 v)
 //   [Te0[x] copy 0..31][Te1[x] copy 0..31],
 // so the address of byte r of s is (byte_r(s) << 8) | (lane&31)*4 -- a single
 // v_perm -- with Te1 at immediate offset +128.  Te2 / Te3 are Te0 / Te1
-// rotated by 16.  64 KiB of LDS.
-constexpr int kTeBytes = 256 * 256;
+// rotated by 16.  64 KiB of LDS (kTeBytes, qpp_te4.h).
 
 struct LdsTe {
+    static constexpr bool kFourTables = false;
     const uint8_t *te;  // LDS base of the 64 KiB image
     uint32_t lo;        // (lane & 31) * 4
     template <int R>
@@ -330,6 +292,38 @@ struct LdsTe {
     __device__ __forceinline__ uint32_t fr3(uint32_t s) const { return *(const uint32_t *)(te + 128 + addr<3>(s)); }
 };
 
+// The four-table image (128 KiB: the close-from-LDS form of k_gcm): Te2 | Te3
+// in a second 64 KiB after Te0 | Te1, in the same row layout, so rows 2 and 3
+// need no rotate.  The second half lies beyond the 16-bit ds_read immediate,
+// so its bit 16 rides in the per-lane constant, and the one v_perm of the
+// address takes result byte 2 from it for rows 2 and 3 and a zero for rows 0
+// and 1 (and for the final round, which reads S(x) from the low half).
+struct LdsTe4 {
+    static constexpr bool kFourTables = true;
+    const uint8_t *te;  // LDS base of the 128 KiB image
+    uint32_t lo;        // (lane & 31) * 4 | 0x10000
+    // HI: the high half
+    template <int R, bool HI>
+    __device__ __forceinline__ uint32_t addr(uint32_t s) const
+    {
+        // result byte0 = lo.byte0, byte1 = s.byte R, byte2 = lo.byte2 (= 1) or 0, byte3 = 0
+        return __builtin_amdgcn_perm(s, lo, (HI ? 0x0c020000u : 0x0c0c0000u) | ((4u + R) << 8));
+    }
+    __device__ __forceinline__ uint32_t t0(uint32_t s) const { return *(const uint32_t *)(te + addr<0, false>(s)); }
+    __device__ __forceinline__ uint32_t t1(uint32_t s) const { return *(const uint32_t *)(te + 128 + addr<1, false>(s)); }
+    __device__ __forceinline__ uint32_t t2(uint32_t s) const { return *(const uint32_t *)(te + addr<2, true>(s)); }
+    __device__ __forceinline__ uint32_t t3(uint32_t s) const { return *(const uint32_t *)(te + 128 + addr<3, true>(s)); }
+    // final round, as LdsTe's
+    __device__ __forceinline__ uint32_t f0(uint32_t s) const { return (fr0(s) >> 8) & 0xffu; }
+    __device__ __forceinline__ uint32_t f1(uint32_t s) const { return fr1(s) & 0xff00u; }
+    __device__ __forceinline__ uint32_t f2(uint32_t s) const { return fr2(s) & 0xff0000u; }
+    __device__ __forceinline__ uint32_t f3(uint32_t s) const { return fr3(s) & 0xff000000u; }
+    __device__ __forceinline__ uint32_t fr0(uint32_t s) const { return *(const uint32_t *)(te + addr<0, false>(s)); }
+    __device__ __forceinline__ uint32_t fr1(uint32_t s) const { return *(const uint32_t *)(te + addr<1, false>(s)); }
+    __device__ __forceinline__ uint32_t fr2(uint32_t s) const { return *(const uint32_t *)(te + 128 + addr<2, false>(s)); }
+    __device__ __forceinline__ uint32_t fr3(uint32_t s) const { return *(const uint32_t *)(te + 128 + addr<3, false>(s)); }
+};
+
 // One output column of the final round from the raw lookups of LdsTe::fr0..3:
 // bytes S(a0) S(a1) by one v_perm, S(a2) S(a3) by another, then (| , ^ k) in
 // one v_bitop3 -- 3 VALU instead of 4 masks / shifts, 3 ors and an xor.
@@ -359,9 +353,11 @@ struct ConstTe {
 // (MixColumns coefficients); the final round substitutes only.
 // Rounds R0..NR on a state that already holds round R0-1's output.  With
 // KROT the keys of rounds R0..NR-1 are stored rotated right by 16 (KeySlot::
-// rkr) and each column costs 3 VALU besides its lookups:
+// rkr) and each column costs 3 VALU besides its lookups (te_col2):
 //   xor3(T0(a), T1(b), rotl16(xor3(T0(c), T1(d), rotr16(k))))
-// instead of xor3(xor3(T0(a), T1(b), rotl16 T0(c)), rotl16 T1(d), k).
+// instead of xor3(xor3(T0(a), T1(b), rotl16 T0(c)), rotl16 T1(d), k).  A
+// four-table lookup object (TE::kFourTables) takes plain keys and 2 VALU a
+// column (te_col4); KROT then only selects the one-round-trip schedule.
 template <int NR, int R0, bool KROT = false, class TE>
 __device__ __forceinline__ u32x4 aes_rounds(u32x4 st, const uint32_t *rk, const TE &T)
 {
@@ -374,15 +370,28 @@ __device__ __forceinline__ u32x4 aes_rounds(u32x4 st, const uint32_t *rk, const 
             // all 16 lookups of the round in flight before the first use: one
             // LDS round trip per round (the scheduler otherwise interleaves
             // waits after every few reads to save registers)
-            const uint32_t a0 = T.t0(s0), a1 = T.t1(s1), a2 = T.t2r(s2), a3 = T.t3r(s3);
-            const uint32_t b0 = T.t0(s1), b1 = T.t1(s2), b2 = T.t2r(s3), b3 = T.t3r(s0);
-            const uint32_t c0 = T.t0(s2), c1 = T.t1(s3), c2 = T.t2r(s0), c3 = T.t3r(s1);
-            const uint32_t d0 = T.t0(s3), d1 = T.t1(s0), d2 = T.t2r(s1), d3 = T.t3r(s2);
-            __builtin_amdgcn_sched_barrier(0);
-            t0 = xor3(a0, a1, rotl(xor3(a2, a3, k[0]), 16));
-            t1 = xor3(b0, b1, rotl(xor3(b2, b3, k[1]), 16));
-            t2 = xor3(c0, c1, rotl(xor3(c2, c3, k[2]), 16));
-            t3 = xor3(d0, d1, rotl(xor3(d2, d3, k[3]), 16));
+            if constexpr (TE::kFourTables) {
+                // plain keys, every row from its own table: no rotate
+                const uint32_t a0 = T.t0(s0), a1 = T.t1(s1), a2 = T.t2(s2), a3 = T.t3(s3);
+                const uint32_t b0 = T.t0(s1), b1 = T.t1(s2), b2 = T.t2(s3), b3 = T.t3(s0);
+                const uint32_t c0 = T.t0(s2), c1 = T.t1(s3), c2 = T.t2(s0), c3 = T.t3(s1);
+                const uint32_t d0 = T.t0(s3), d1 = T.t1(s0), d2 = T.t2(s1), d3 = T.t3(s2);
+                __builtin_amdgcn_sched_barrier(0);
+                t0 = te_col4(a0, a1, a2, a3, k[0]);
+                t1 = te_col4(b0, b1, b2, b3, k[1]);
+                t2 = te_col4(c0, c1, c2, c3, k[2]);
+                t3 = te_col4(d0, d1, d2, d3, k[3]);
+            } else {
+                const uint32_t a0 = T.t0(s0), a1 = T.t1(s1), a2 = T.t2r(s2), a3 = T.t3r(s3);
+                const uint32_t b0 = T.t0(s1), b1 = T.t1(s2), b2 = T.t2r(s3), b3 = T.t3r(s0);
+                const uint32_t c0 = T.t0(s2), c1 = T.t1(s3), c2 = T.t2r(s0), c3 = T.t3r(s1);
+                const uint32_t d0 = T.t0(s3), d1 = T.t1(s0), d2 = T.t2r(s1), d3 = T.t3r(s2);
+                __builtin_amdgcn_sched_barrier(0);
+                t0 = te_col2(a0, a1, a2, a3, k[0]);
+                t1 = te_col2(b0, b1, b2, b3, k[1]);
+                t2 = te_col2(c0, c1, c2, c3, k[2]);
+                t3 = te_col2(d0, d1, d2, d3, k[3]);
+            }
         } else {
             t0 = xor3(xor3(T.t0(s0), T.t1(s1), T.t2(s2)), T.t3(s3), k[0]);
             t1 = xor3(xor3(T.t0(s1), T.t1(s2), T.t2(s3)), T.t3(s0), k[1]);
@@ -465,7 +474,8 @@ __device__ __forceinline__ CtrCache ctr_cache(u32x4 nonce, const uint32_t *rk, c
 }
 
 // E_K(nonce || BE32(cb)), 1 <= cb < 256, from the packet's cache.  rk holds
-// plain keys for rounds 0..2 and NR and rotated ones (rkr) for 3..NR-1.
+// plain keys for rounds 0..2 and NR and rotated ones (rkr) for 3..NR-1
+// (plain ones throughout for a four-table lookup object).
 template <int NR, class TE>
 __device__ __forceinline__ u32x4 aes_ctr(const CtrCache &c, uint32_t cb, const uint32_t *rk,
                                          const TE &T)
@@ -500,17 +510,25 @@ __device__ __forceinline__ void aes_ctr2(const CtrCache &c, uint32_t cb0, uint32
             for (int col = 0; col < 4; ++col) {
                 e[b][4 * col + 0] = T.t0(s[b][col]);
                 e[b][4 * col + 1] = T.t1(s[b][(col + 1) & 3]);
-                e[b][4 * col + 2] = T.t2r(s[b][(col + 2) & 3]);
-                e[b][4 * col + 3] = T.t3r(s[b][(col + 3) & 3]);
+                if constexpr (TE::kFourTables) {
+                    e[b][4 * col + 2] = T.t2(s[b][(col + 2) & 3]);
+                    e[b][4 * col + 3] = T.t3(s[b][(col + 3) & 3]);
+                } else {
+                    e[b][4 * col + 2] = T.t2r(s[b][(col + 2) & 3]);
+                    e[b][4 * col + 3] = T.t3r(s[b][(col + 3) & 3]);
+                }
             }
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
 #pragma unroll
-            for (int col = 0; col < 4; ++col)
-                s[b][col] = xor3(e[b][4 * col], e[b][4 * col + 1],
-                                 rotl(xor3(e[b][4 * col + 2], e[b][4 * col + 3], k[col]), 16));
+            for (int col = 0; col < 4; ++col) {
+                if constexpr (TE::kFourTables)
+                    s[b][col] = te_col4(e[b][4 * col], e[b][4 * col + 1], e[b][4 * col + 2], e[b][4 * col + 3], k[col]);
+                else
+                    s[b][col] = te_col2(e[b][4 * col], e[b][4 * col + 1], e[b][4 * col + 2], e[b][4 * col + 3], k[col]);
+            }
         }
     }
     const uint32_t *k = rk + 4 * NR;

@@ -97,6 +97,31 @@ __device__ __forceinline__ void load_te(uint8_t *te)
     }
 }
 
+// The four-table image (LdsTe4): both halves from the same 4 table reads per
+// thread of a 1024-thread workgroup, still one memory round trip.  A function
+// of its own, so the two-table callers keep the fill they have.
+template <int NT>
+__device__ __forceinline__ void load_te4(uint8_t *te)
+{
+    constexpr int kIters = (256 * 16 + NT - 1) / NT;
+    uint32_t v0[kIters];
+#pragma unroll
+    for (int k = 0; k < kIters; ++k) {
+        const int i = (int)threadIdx.x + k * NT;
+        v0[k] = i < 256 * 16 ? c_aes.te0[i >> 4] : 0u;
+    }
+#pragma unroll
+    for (int k = 0; k < kIters; ++k) {
+        const int i = (int)threadIdx.x + k * NT;
+        if (i < 256 * 16) {
+            const int x = i >> 4, part = i & 15;
+            const uint32_t lo = te_image_word(v0[k], 0, part), hi = te_image_word(v0[k], 1, part);
+            *(u32x4 *)(te + x * 256 + part * 16) = u32x4{lo, lo, lo, lo};
+            *(u32x4 *)(te + kTeBytes + x * 256 + part * 16) = u32x4{hi, hi, hi, hi};
+        }
+    }
+}
+
 // ------------------------------------------------------- packet numbers --
 
 // decode_packet_number (quic/packet.py:118-132).  Bit-exact with the
@@ -633,7 +658,10 @@ __device__ __forceinline__ u32x4 gcm_packet(const Pkt &P, const KeySlot *ks, con
                                             const uint8_t *te, const Bufs &B, uint32_t ioff, uint32_t ooff,
                                             u32x4 &got_tag)
 {
-    const LdsTe T{te, (lane_fresh() & 31) * 4};
+    // CLDS: the image holds four tables
+    typedef std::conditional_t<CLDS, LdsTe4, LdsTe> Te;
+    auto te_now = [&]() -> Te { return Te{te, (lane_fresh() & 31) * 4 | (CLDS ? 0x10000u : 0u)}; };
+    const Te T = te_now();
     const int hlen = P.hlen, clen = P.clen;
     const int n_a = (hlen + 15) >> 4, n_c = (clen + 15) >> 4, za = n_a > 0 ? 1 : 0;
     const int n_g = za + n_c + 1, pad = gcm_pad<BPL>(n_g), S = (n_g + pad) / (4 * BPL);
@@ -665,11 +693,24 @@ __device__ __forceinline__ u32x4 gcm_packet(const Pkt &P, const KeySlot *ks, con
 
     // x * H^(pw + 1), pw possibly different in each lane: the multiplies
     // outside the step loop.  From the workgroup's LDS copy of the 4-bit tables
-    // when it holds this wave's slot (CLDS launches; read where used, not
-    // kept live across the step loop), else from the slot's global tables.
-    auto mul_pow = [&](u32x4 x, uint32_t pw) -> u32x4 {
+    // of H^1 and H^2 when it holds this wave's slot (CLDS launches; read where
+    // used, not kept live across the step loop), else from the slot's global
+    // tables of all four powers.  The copy gives H^3 and H^4 (two_c: the
+    // close, pw = 3 - j in lane j) in two multiplies: by H^2 where pw >= 2
+    // (lanes 0, 1; lanes 2, 3 keep their value), then by H^2 where pw is odd
+    // (lanes 0, 2) and by H^1 where it is even (lanes 1, 3).
+    auto mul_pow = [&](u32x4 x, uint32_t pw, auto two_c) -> u32x4 {
         if constexpr (CLDS) {
-            if (G.close_resident()) return ghash_mul(x, G.ctab, pw * (uint32_t)kGhashPowBytes);
+            if (G.close_resident()) {
+                if constexpr (decltype(two_c)::value) {
+                    const u32x4 m = ghash_mul(x, G.ctab, (uint32_t)kGhashPowBytes);
+                    const bool two = (lane_fresh() & 2) == 0;  // pw >= 2
+                    x = u32x4{two ? m.x : x.x, two ? m.y : x.y, two ? m.z : x.z, two ? m.w : x.w};
+                    return ghash_mul(x, G.ctab, (lane_fresh() & 1) ? 0u : (uint32_t)kGhashPowBytes);
+                } else {
+                    return ghash_mul(x, G.ctab, pw * (uint32_t)kGhashPowBytes);  // pw < kClosePowers
+                }
+            }
         }
         return ghash_mul_global(x, G.global(pw));
     };
@@ -689,7 +730,7 @@ __device__ __forceinline__ u32x4 gcm_packet(const Pkt &P, const KeySlot *ks, con
         }
         a = keep_bytes(a, min(16, hlen - 16 * g));
         if (!ENC && P.hp) a ^= hp_pattern(16 * g, P.mask, P.fbm, P.pn_off, P.pn_len);
-        if (g > 0) z = mul_pow(z, 0u);  // H^1
+        if (g > 0) z = mul_pow(z, 0u, std::false_type{});  // H^1
         z ^= a;
     }
     // the header out: unprotect (mask known) and protect without HP now;
@@ -709,7 +750,7 @@ __device__ __forceinline__ u32x4 gcm_packet(const Pkt &P, const KeySlot *ks, con
     // produced (keystream ksl): the tag is then the quad's xor of acc
     auto close = [&](u32x4 ksl) {
         const uint32_t lf = lane_fresh();
-        acc = mul_pow(acc, 3u - (lf & 3));
+        acc = mul_pow(acc, 3u - (lf & 3), std::true_type{});
         if ((lf & 3) == 3) acc ^= ksl;
     };
     // the output side of one block given its keystream: CT block i (input
@@ -744,7 +785,7 @@ __device__ __forceinline__ u32x4 gcm_packet(const Pkt &P, const KeySlot *ks, con
     // one block (BPL = 1)
     auto step = [&](int i, bool last, auto first_c, u32x4 raw) {
         (void)first_c;
-        const LdsTe Tl{te, (lane_fresh() & 31) * 4};
+        const Te Tl = te_now();
         const bool is_ct = i >= 0 && 16 * i < clen;
         const u32x4 ksb = aes_ctr<NR>(cc, is_ct ? (uint32_t)(i + 2) : 1u, rk, Tl);
         acc ^= blk_out(i, ksb, raw);
@@ -756,7 +797,7 @@ __device__ __forceinline__ u32x4 gcm_packet(const Pkt &P, const KeySlot *ks, con
     // BPL = 2: lane blocks i and i + 4 (CT indices) in one step
     auto step2 = [&](int i, bool last, u32x4 raw0, u32x4 raw1, auto first_c) {
         constexpr bool first = decltype(first_c)::value;
-        const LdsTe Tl{te, (lane_fresh() & 31) * 4};
+        const Te Tl = te_now();
         const uint32_t cb0 = (i >= 0 && 16 * i < clen) ? (uint32_t)(i + 2) : 1u;
         const uint32_t cb1 = (i + 4 >= 0 && 16 * (i + 4) < clen) ? (uint32_t)(i + 6) : 1u;
         u32x4 ks0, ks1;
@@ -1302,18 +1343,21 @@ constexpr int kTabEntries = 4;
 //
 // Close-from-LDS form (CLDS; launch_packets: unplanned 1024-thread launches
 // with one key of the suite in the table): one H^4 entry, and in the space of
-// the other three a copy of one slot's 4-bit-window tables of H^1..H^4
-// (32 KiB, the bytes ghash_mul_global reads), fetched with the first entry
-// load of the workgroup.  The packets of that slot then take their
-// multiplies outside the step loop (associated data, each lane's closing
-// H^(4-j)) from LDS instead of 32 gathered global loads per lane
-// (gcm_packet); a packet of any other slot keeps the global tables.
+// the other three a copy of one slot's 4-bit-window tables of H^1 and H^2
+// (16 KiB, the first bytes ghash_mul_global reads), fetched with the first
+// entry load of the workgroup.  The packets of that slot then take their
+// multiplies outside the step loop (associated data by H^1, each lane's
+// closing H^(4-j) as two multiplies by H^2 or H^1) from LDS instead of 32
+// gathered global loads per lane (gcm_packet); a packet of any other slot
+// keeps the global tables.  What the smaller copy frees goes to the AES
+// image, which in this form holds four tables (LdsTe4, 128 KiB).
 template <int WG, bool CLDS = false>
 constexpr int gcm_tab_entries() { return (WG == 512 || CLDS) ? 1 : kTabEntries; }
 static_assert(kGhLdsEntry % 1024 == 0, "LDS-DMA pieces of 1 KiB");
-constexpr int kCloseTabBytes = kGhashPowers * kGhashPowBytes;
-static_assert(kCloseTabBytes % 1024 == 0 && kCloseTabBytes <= (kTabEntries - 1) * kGhLdsEntry,
-              "the close tables fit the space of the H^4 entries they replace");
+constexpr int kClosePowers = 2;  // H^1 and H^2: the first two powers of a slot's tables
+constexpr int kCloseTabBytes = kClosePowers * kGhashPowBytes;
+static_assert(kClosePowers <= kGhashPowers && kCloseTabBytes % 1024 == 0 && kCloseTabBytes == 16 * 1024,
+              "the close tables: 16 LDS-DMA pieces of 1 KiB, the head of the slot's 4-bit tables");
 
 // Watchdog events since the library loaded (tab_acquire gave up on a GHASH
 // table entry, or a pair launch's hand-over timed out: the packets concerned
@@ -1340,9 +1384,9 @@ struct __attribute__((aligned(16))) GcmSmem {
     // the 5-bit window address), then the AES image, whose base stays within
     // the 16-bit ds_read immediate range
     uint8_t h4[NE][kGhLdsEntry];              // 14 KiB each
-    uint8_t ctab[CLDS ? kCloseTabBytes : 0];  // CLDS: slot cslot's 4-bit tables of H^1..H^4   32 KiB
+    uint8_t ctab[CLDS ? kCloseTabBytes : 0];  // CLDS: slot cslot's 4-bit tables of H^1, H^2   16 KiB
     uint32_t cslot[CLDS ? 4 : 0];             // CLDS: [0] the slot ctab holds (kNoSlot: none yet)
-    uint8_t te[kTeBytes];                     // Te0|Te1 x 32 bank copies   64 KiB
+    uint8_t te[CLDS ? 2 * kTeBytes : kTeBytes];  // Te0|Te1 x 32 bank copies 64 KiB; CLDS: and Te2|Te3, 128 KiB
     uint32_t eslot[NE];                       // slot held by entry e (kNoSlot: none)
     uint32_t eref[NE];                        // waves running entry e's slot
     uint32_t eready[NE];                      // entry e's table has landed
@@ -1353,6 +1397,10 @@ struct __attribute__((aligned(16))) GcmSmem {
     uint32_t wslot[WG / 64];                  // per wave: the slot it is running
     uint32_t went[WG / 64];                   // per wave: that slot's table entry
 };
+
+typedef GcmSmem<1024, true> GcmSmemClose;
+static_assert(sizeof(GcmSmem<1024, true>) <= 163840, "the close-from-LDS form fits a workgroup's LDS");
+static_assert(offsetof(GcmSmemClose, te) + 128 < 65536, "the image's base rides in the ds_read immediate");
 
 // Entry of slot `cur` for the calling wave (wave-uniform control flow):
 // found, or loaded into a free entry.  Lane 0 does the bookkeeping under the
@@ -1433,7 +1481,7 @@ __device__ uint32_t tab_acquire(SM &sm, const uint8_t *gtab, uint32_t cur)
             __builtin_amdgcn_global_load_lds((gptr_t)(src + c * 1024 + l * 16), (lptr_t)(sm.h4[e] + c * 1024),
                                              16, 0, 0);
         if constexpr (SM::kClose) {
-            // H^1..H^4 in 4-bit windows, as they lie in global memory; landed,
+            // H^1, H^2 in 4-bit windows, as they lie in global memory; landed,
             // like the entry, before any wave is told the entry is ready
             if (load & 2u) {
                 const uint8_t *src4 = gtab + (size_t)cur * kGhashTabBytes;
@@ -1520,7 +1568,8 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
     // across the packet loops: at 128 VGPRs anything live across the GCM step
     // loop is spilled to scratch (HBM traffic and latency).
     auto tid_now = [&]() -> uint32_t { return (wv << 6) | lane_fresh(); };
-    load_te<WG>(sm.te);
+    if constexpr (CLDS) load_te4<WG>(sm.te);
+    else load_te<WG>(sm.te);
     if (threadIdx.x < gcm_tab_entries<WG, CLDS>()) {
         sm.eslot[threadIdx.x] = kNoSlot;
         sm.eref[threadIdx.x] = 0u;
@@ -1601,10 +1650,11 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
             Pkt P = pkt_begin<ENC, SUITE>(d, pre, gin, gout, ks, T);
             if (P.status == QPP_S_OK) {
                 // plain keys for rounds 0-2 (counter cache) and NR, rotated between
+                // (CLDS: four tables, plain keys throughout)
                 uint32_t rk[4 * (kNR + 1)];
 #pragma unroll
                 for (int i = 0; i < 4 * (kNR + 1); ++i)
-                    rk[i] = __builtin_amdgcn_readfirstlane((i >= 12 && i < 4 * kNR) ? ks->rkr[i] : ks->rk[i]);
+                    rk[i] = __builtin_amdgcn_readfirstlane((!CLDS && i >= 12 && i < 4 * kNR) ? ks->rkr[i] : ks->rk[i]);
                 const uint64_t ioff = d.in_off - bi, ooff = d.out_off - bo;
                 if (item_span_ok<ENC>(P, ioff, ooff)) {
                     const Bufs B{
