@@ -164,6 +164,19 @@ class PacketEngine:
                            int(n_long), _ptr(conn_slot), _ptr(conn_expected), int(n_conn), int(flags), _ptr(desc),
                            _ptr(walk), _ptr(walk_n), self._stream(stream))
 
+    def route_accept(self, offs, lens, n: int, inbuf, route, long_idx, n_long: int, walk, walk_n, acc_row,
+                     acc_slot, n_acc: int, ini, desc, acc, accept_flags: int = 0, flags: int = 0,
+                     stream=None) -> None:
+        """qpp_route_accept on device buffers, after route() and route_walk()
+        on the same stream: the unrouted Initials a server may answer among
+        the candidates `acc_row` (uint32 rows of `long_idx`, strictly
+        increasing), with two key slots each in `acc_slot` (uint32), into
+        INITIAL records (`ini`), ACCEPT records (`acc`) and the accepted
+        datagrams' DESC records."""
+        _crypto.route_accept(_ptr(offs), _ptr(lens), int(n), _ptr(inbuf), _ptr(route), _ptr(long_idx), int(n_long),
+                             _ptr(walk), _ptr(walk_n), _ptr(acc_row), _ptr(acc_slot), int(n_acc), int(accept_flags),
+                             int(flags), _ptr(ini), _ptr(desc), _ptr(acc), self._stream(stream))
+
     def route_walk_unprotect_host(self, cid_map, cid_len: int, offs, lens, data, long_idx, conn_slot,
                                   conn_expected, out_len: int, flags: int = 0):
         """Route, walk the long-header datagrams `long_idx` and unprotect a

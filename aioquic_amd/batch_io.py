@@ -175,6 +175,25 @@ class KeySlots:
         take = self._free[::-1][:n]
         return take + list(range(high, high + n - len(take)))
 
+    def room(self) -> int:
+        """How many more slots the table takes before an assign() or a
+        reserve() would clear and refill it."""
+        if self._inbox:
+            self._drain()
+        return self.capacity - len(self._keep)
+
+    def give_back(self, slots) -> None:
+        """Reserved slots that nothing adopted, after a device call installed
+        keys in some of them on its own (receive.accept_routed): their device
+        entries are cleared in one call and the slots are free again."""
+        held = set(self._keep)
+        back = [s for s in slots if s not in held]
+        if not back:
+            return
+        free = set(self._free)
+        self._free += [s for s in back if s not in free]
+        self.table.clear(np.asarray(sorted(back), np.uint32).tobytes())
+
     def adopt(self, slots, triples) -> None:
         """Bind reserved slots that already hold their keys on the device to
         their (aead, hp, key_phase): nothing is left to commit for them."""
@@ -308,20 +327,32 @@ def setup_initial_batch(pairs, cids, is_client, versions, slots: Optional[KeySlo
     recs["slot_server"] = taken[1::2]
     km, secrets = slots.table.derive_initial(recs.tobytes())
     km = np.frombuffer(km, dtype=L.KEY_MATERIAL)
+    built = [_initial_directions(km, secrets, i, roles[i]) for i in range(n)]
+    _install_initial(slots, pairs, built, vers)
+
+
+def _initial_directions(km, secrets: bytes, i: int, is_client: bool) -> list:
+    """(recv, send) of record i of a derive_initial result (km: its key
+    material as a layout.KEY_MATERIAL array, secrets: its secrets), each
+    (slot, secret, aead, hp)."""
     suite = crypto_mod._SUITES[crypto_mod.INITIAL_CIPHER_SUITE]
-    built = []  # per pair: (recv, send), each (slot, secret, aead, hp)
-    for i in range(n):
-        both = []
-        for label in crypto_mod._INITIAL_LABELS[roles[i]]:
-            k = 2 * i + (label == b"server in")
-            m = km[k]
-            aead = crypto_mod.AEAD(suite.aead_name, m["key"][: suite.key_len].tobytes(), m["iv"].tobytes())
-            hp = crypto_mod.HeaderProtection(suite.hp_name, m["hp"][: suite.key_len].tobytes())
-            both.append((int(m["slot"]), secrets[32 * k: 32 * k + 32], aead, hp))
-        built.append(both)
+    both = []
+    for label in crypto_mod._INITIAL_LABELS[is_client]:
+        k = 2 * i + (label == b"server in")
+        m = km[k]
+        aead = crypto_mod.AEAD(suite.aead_name, m["key"][: suite.key_len].tobytes(), m["iv"].tobytes())
+        hp = crypto_mod.HeaderProtection(suite.hp_name, m["hp"][: suite.key_len].tobytes())
+        both.append((int(m["slot"]), secrets[32 * k: 32 * k + 32], aead, hp))
+    return both
+
+
+def _install_initial(slots: KeySlots, pairs, built, versions) -> None:
+    """The end of setup_initial for pairs whose keys a device call has derived
+    and installed (built: _initial_directions per pair): the slots are bound
+    to their objects and every context ends as pair.setup_initial leaves it."""
     # the device slots were written with key phase 0, which is a fresh context's
     slots.adopt([d[0] for both in built for d in both], [(d[2], d[3], 0) for both in built for d in both])
-    for pair, both, version in zip(pairs, built, vers):
+    for pair, both, version in zip(pairs, built, versions):
         for ctx, (_, secret, aead, hp) in zip((pair.recv, pair.send), both):
             ctx.cipher_suite, ctx.secret, ctx.version = crypto_mod.INITIAL_CIPHER_SUITE, secret, version
             ctx.aead, ctx.hp = aead, hp

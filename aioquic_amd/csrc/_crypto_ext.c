@@ -35,6 +35,8 @@
  *   route_unprotect_host(table, map, cid_len, offs, lens, data, conn_slot, conn_expected,
  *                        flags, out_len) -> (out, desc, route, results)
  *   receive_routed(...)                             receive.receive_routed's C path
+ *   route_accept(...), receive_accept(...)          unrouted Initials accepted on the device:
+ *                                                   the device form, receive.accept_routed's C path
  *
  * Threads: host-buffer calls release the GIL.  Each OS thread gets its own
  * qpp_session (pinned staging + streams; quic_pp.h: a session is single-
@@ -1230,6 +1232,35 @@ static PyObject *py_route_walk_launches(PyObject *m, PyObject *unused)
     return PyLong_FromUnsignedLongLong(qpp_route_walk_launches());
 }
 
+/* route_accept(off_ptr, len_ptr, n, in_ptr, route_ptr, long_ptr, n_long, walk_ptr, walk_n_ptr, row_ptr, slot_ptr,
+ *              n_acc, accept_flags, desc_flags, ini_ptr, desc_ptr, acc_ptr, stream) */
+static PyObject *py_route_accept(PyObject *m, PyObject *args)
+{
+    unsigned long long op, lp, ip, rp, xp, wp, wnp, arp, asp, inip, dp, accp, sp;
+    unsigned int n, n_long, n_acc, accept_flags, flags;
+    if (!PyArg_ParseTuple(args, "KKIKKKIKKKKIIIKKKK", &op, &lp, &n, &ip, &rp, &xp, &n_long, &wp, &wnp, &arp, &asp,
+                          &n_acc, &accept_flags, &flags, &inip, &dp, &accp, &sp))
+        return NULL;
+    if (flags > 0xffff) {
+        PyErr_SetString(PyExc_ValueError, "descriptor flags are 16 bits");
+        return NULL;
+    }
+    int rc = qpp_route_accept(as_ptr(op), as_ptr(lp), n, as_ptr(ip), as_ptr(rp), as_ptr(xp), n_long, as_ptr(wp),
+                              as_ptr(wnp), as_ptr(arp), as_ptr(asp), n_acc, accept_flags, (uint16_t)flags,
+                              as_ptr(inip), as_ptr(dp), as_ptr(accp), as_ptr(sp));
+    if (rc == QPP_E_ARG) {
+        PyErr_SetString(PyExc_ValueError, "bad route_accept arguments (a null buffer, or an unknown accept flag)");
+        return NULL;
+    }
+    if (check_rc(rc) < 0) return NULL;
+    Py_RETURN_NONE;
+}
+
+static PyObject *py_route_accept_launches(PyObject *m, PyObject *unused)
+{
+    return PyLong_FromUnsignedLongLong(qpp_route_accept_launches());
+}
+
 static int host_call(int enc, qpp_keytab *kt, const void *desc, uint32_t n, const void *in,
                      size_t in_len, void *out, size_t out_len, void *res)
 {
@@ -2340,18 +2371,35 @@ done:
  * (walk_results) without another launch.
  * No walk (None, nothing of the state consulted again) with walk == 0, or
  * when a long-header datagram belongs to a known connection and the walk's
- * arrays were not given: the caller's general path takes the batch then. */
-static PyObject *py_receive_routed(PyObject *m, PyObject *args)
+ * arrays were not given: the caller's general path takes the batch then.
+ *
+ * receive_accept(the same arguments, acc_row_u32, acc_slot_u32, accept_flags)
+ *     -> (route, None, None | (long_idx, walk records, walk counts, descriptors, results, output),
+ *         (accept records, key material, secrets))
+ * receive_routed for a server that also takes on new connections: the call
+ * is qpp_session_accept_unprotect, with the candidates acc_row (rows of the
+ * listed long-header datagrams, in the order this call lists them: the
+ * datagrams whose first byte has bit 7 set, in batch order) and two key slots
+ * each in acc_slot.  The walk's arrays must be given and walk != 0.  The
+ * in-order walk is always the caller's: the third item carries what the
+ * device found whenever a long-header datagram was listed.  The fourth item
+ * holds the packed qpp_accept_rec, 2 x qpp_key_material and 2 x 32 secret
+ * bytes of every candidate. */
+static PyObject *receive_routed_impl(PyObject *args, int accept)
 {
     PyObject *t, *mo, *dgs, *rec_type, *ptype, *epoch;
-    const char *a_pair, *a_space, *a_pslot, *a_sexp, *a_closed, *a_kslot, *a_kexp;
-    Py_ssize_t l_pair, l_space, l_pslot, l_sexp, l_closed, l_kslot, l_kexp;
-    unsigned int cid_len;
+    const char *a_pair, *a_space, *a_pslot, *a_sexp, *a_closed, *a_kslot, *a_kexp, *a_arow = NULL, *a_aslot = NULL;
+    Py_ssize_t l_pair, l_space, l_pslot, l_sexp, l_closed, l_kslot, l_kexp, l_arow = 0, l_aslot = 0;
+    unsigned int cid_len, accept_flags = 0;
     int walk;
-    if (!PyArg_ParseTuple(args, "OOIO!y#y#y#y#y#y#OOOy#i", &t, &mo, &cid_len, &PyList_Type, &dgs, &a_pair, &l_pair,
-                          &a_space, &l_space, &a_pslot, &l_pslot, &a_sexp, &l_sexp, &a_kslot, &l_kslot, &a_kexp,
-                          &l_kexp, &rec_type, &ptype, &epoch,
-                          &a_closed, &l_closed, &walk))
+    if (!(accept ? PyArg_ParseTuple(args, "OOIO!y#y#y#y#y#y#OOOy#iy#y#I", &t, &mo, &cid_len, &PyList_Type, &dgs, &a_pair,
+                                    &l_pair, &a_space, &l_space, &a_pslot, &l_pslot, &a_sexp, &l_sexp, &a_kslot,
+                                    &l_kslot, &a_kexp, &l_kexp, &rec_type, &ptype, &epoch, &a_closed, &l_closed, &walk,
+                                    &a_arow, &l_arow, &a_aslot, &l_aslot, &accept_flags)
+                 : PyArg_ParseTuple(args, "OOIO!y#y#y#y#y#y#OOOy#i", &t, &mo, &cid_len, &PyList_Type, &dgs, &a_pair,
+                                    &l_pair, &a_space, &l_space, &a_pslot, &l_pslot, &a_sexp, &l_sexp, &a_kslot,
+                                    &l_kslot, &a_kexp, &l_kexp, &rec_type, &ptype, &epoch, &a_closed, &l_closed,
+                                    &walk)))
         return NULL;
     qpp_keytab *kt = as_table(t);
     qpp_cidmap *map = kt ? as_cidmap(mo) : NULL;
@@ -2383,6 +2431,12 @@ static PyObject *py_receive_routed(PyObject *m, PyObject *args)
         PyErr_SetString(PyExc_ValueError, "batch too large");
         return NULL;
     }
+    const Py_ssize_t na = l_arow / 4;
+    if (accept && (l_arow % 4 || l_aslot != 8 * na || na > n || !walk || !(l_kslot || l_kexp || nc == 0))) {
+        PyErr_SetString(PyExc_ValueError, "acc_row: whole u32 items, no more than datagrams; acc_slot: two u32 each; "
+                                          "the walk's arrays are required");
+        return NULL;
+    }
     PyTypeObject *tp = (PyTypeObject *)rec_type;
     allocfunc alloc = (allocfunc)PyType_GetSlot(tp, Py_tp_alloc);
     if (!alloc) return NULL;
@@ -2410,7 +2464,13 @@ static PyObject *py_receive_routed(PyObject *m, PyObject *args)
     size_t *ol = (size_t *)malloc((2 * (size_t)n + 1) * sizeof(size_t));
     PyObject *ret = NULL, *route = NULL, *recs = NULL, *deferred = NULL, *sexp_out = NULL, *closed_out = NULL;
     PyObject *empty = NULL, *minus1 = NULL, *zero = NULL, *s_key = NULL, *s_dec = NULL, *s_rsv = NULL, *s_closed = NULL;
-    PyObject *walked = NULL, *longs = NULL;
+    PyObject *walked = NULL, *longs = NULL, *acc = NULL, *km = NULL, *secrets = NULL;
+    if (accept) {
+        acc = PyBytes_FromStringAndSize(NULL, na * (Py_ssize_t)sizeof(qpp_accept_rec));
+        km = PyBytes_FromStringAndSize(NULL, na * 2 * (Py_ssize_t)sizeof(qpp_key_material));
+        secrets = PyBytes_FromStringAndSize(NULL, na * 64);
+        if (!acc || !km || !secrets) goto nomem;
+    }
     if (!offs || !cexp || !lens || !cslot || !conn_of || !slot_of || !dg || !lidx || !cd || !cs || !cl ||
         !blocked_pair || !blocked_space || !blocked_conn || !od || !os_ || !ol)
         goto nomem;
@@ -2435,6 +2495,10 @@ static PyObject *py_receive_routed(PyObject *m, PyObject *args)
         if (walk && can_walk && len && (cs[i][0] & 0x80)) lidx[nl++] = (uint32_t)i;
     }
     if ((uint64_t)n + 3ull * nl > 0x7fffffffull) nl = 0;  /* past the fused call's limit: the general path */
+    if (accept && na && !nl) {
+        PyErr_SetString(PyExc_ValueError, "candidates without a listed long-header datagram");
+        goto done;
+    }
     const size_t nd = (size_t)n + 3 * (size_t)nl, nd1 = nd ? nd : 1, nl1 = nl ? nl : 1;
     desc = (qpp_desc *)malloc(nd1 * sizeof(qpp_desc));
     res = (qpp_result *)malloc(nd1 * sizeof(qpp_result));
@@ -2456,7 +2520,15 @@ static PyObject *py_receive_routed(PyObject *m, PyObject *args)
         int rc;
         Py_BEGIN_ALLOW_THREADS  /* the snapshot holds every datagram */
         par_copy(cd, cs, cl, (size_t)n, total);
-        if (nl)
+        if (accept)
+            rc = qpp_session_accept_unprotect(ss, kt, map, cid_len, offs, lens, (uint32_t)n, hin, total, lidx, nl,
+                                              (const uint32_t *)a_kslot, (const uint64_t *)a_kexp, (uint32_t)nc, 0,
+                                              (const uint32_t *)a_arow, (const uint32_t *)a_aslot, (uint32_t)na,
+                                              accept_flags, hout, total, desc, (qpp_route_rec *)rr, res, wrec, wn,
+                                              (qpp_accept_rec *)PyBytes_AsString(acc),
+                                              (qpp_key_material *)PyBytes_AsString(km),
+                                              (uint8_t *)PyBytes_AsString(secrets));
+        else if (nl)
             rc = qpp_session_route_walk_unprotect(ss, kt, map, cid_len, offs, lens, (uint32_t)n, hin, total, lidx, nl,
                                                   (const uint32_t *)a_kslot, (const uint64_t *)a_kexp, (uint32_t)nc,
                                                   0, hout, total, desc, (qpp_route_rec *)rr, res, wrec, wn);
@@ -2464,8 +2536,15 @@ static PyObject *py_receive_routed(PyObject *m, PyObject *args)
             rc = qpp_session_route_unprotect(ss, kt, map, cid_len, offs, lens, (uint32_t)n, hin, total, cslot, cexp,
                                              (uint32_t)nc, 0, hout, total, desc, (qpp_route_rec *)rr, res);
         Py_END_ALLOW_THREADS
+        if (accept && rc == QPP_E_ARG) {
+            PyErr_SetString(PyExc_ValueError, "bad accept arguments (acc_row not strictly increasing below the listed "
+                                              "datagrams, a slot outside the table or named twice, or an unknown "
+                                              "flag); nothing was launched");
+            goto done;
+        }
         if (check_rc(rc) < 0) goto done;
     }
+    if (accept) walk = 0;  /* the in-order walk is the caller's */
     /* the records to walk: the short-header datagrams of known connections */
     Py_ssize_t nr = 0;
     for (Py_ssize_t i = 0; i < n && walk; ++i) {
@@ -2493,7 +2572,13 @@ static PyObject *py_receive_routed(PyObject *m, PyObject *args)
             for (int k = 0; k < 6; ++k) Py_XDECREF(f[k]);
             if (!longs) goto done;
         }
-        ret = PyTuple_Pack(3, route, Py_None, longs ? longs : Py_None);
+        if (accept) {
+            PyObject *found = PyTuple_Pack(3, acc, km, secrets);
+            if (found) ret = PyTuple_Pack(4, route, Py_None, longs ? longs : Py_None, found);
+            Py_XDECREF(found);
+        } else {
+            ret = PyTuple_Pack(3, route, Py_None, longs ? longs : Py_None);
+        }
         goto done;
     }
     sexp_out = PyBytes_FromStringAndSize(a_sexp, l_sexp);
@@ -2529,6 +2614,9 @@ done:
     free(offs), free(cexp), free(lens), free(cslot), free(conn_of), free(slot_of), free(dg), free(desc), free(res);
     free(lidx), free(wrec), free(wn);
     Py_XDECREF(longs);
+    Py_XDECREF(acc);
+    Py_XDECREF(km);
+    Py_XDECREF(secrets);
     free(cd), free(cs), free(cl), free(blocked_pair), free(blocked_space), free(blocked_conn), free(od), free(os_);
     free(ol);
     Py_DECREF(dgs);
@@ -2547,6 +2635,9 @@ done:
     Py_XDECREF(s_closed);
     return ret;
 }
+
+static PyObject *py_receive_routed(PyObject *m, PyObject *args) { return receive_routed_impl(args, 0); }
+static PyObject *py_receive_accept(PyObject *m, PyObject *args) { return receive_routed_impl(args, 1); }
 
 /* long_dcids(datagrams) -> None when no bytes object of the list starts with
  * a long header (first byte, bit 7), else the set of the destination CIDs of
@@ -2653,6 +2744,11 @@ static PyMethodDef module_methods[] = {
     {"route_walk_unprotect_host", py_route_walk_unprotect_host, METH_VARARGS,
      "qpp_session_route_walk_unprotect on host buffers"},
     {"route_walk_launches", py_route_walk_launches, METH_NOARGS, "qpp_route_walk_launches()"},
+    {"route_accept", py_route_accept, METH_VARARGS, "qpp_route_accept on device buffers"},
+    {"route_accept_launches", py_route_accept_launches, METH_NOARGS, "qpp_route_accept_launches()"},
+    {"receive_accept", py_receive_accept, METH_VARARGS,
+     "receive_routed with the unrouted Initials among the candidates accepted on the device "
+     "(qpp_session_accept_unprotect)"},
     {"long_dcids", py_long_dcids, METH_VARARGS,
      "long_dcids(datagrams) -> None, or the set of the DCIDs of the datagrams that start with a long header"},
     {"walk_results", py_walk_results, METH_VARARGS, "unprotect_walk's walk over the results of a launch that has run"},

@@ -2677,6 +2677,7 @@ __global__ __launch_bounds__(kXferWG) void k_xfer(const uint8_t *__restrict__ s0
 #include <atomic>
 #include <mutex>
 #include <new>
+#include <vector>
 
 using namespace qpp;
 
@@ -2782,6 +2783,18 @@ static uint32_t keytab_suite_mask(const qpp_keytab *kt)
     for (int s = 0; s < 3; ++s)
         if (kt->n_suite[s]) m |= 1u << s;
     return m;
+}
+
+// The Initial salts' HMAC pad states (k_derive_initial's argument): the same
+// for every call.
+static const qpp_hkdf::InitialSalts &initial_salts()
+{
+    static const qpp_hkdf::InitialSalts salts = [] {
+        qpp_hkdf::InitialSalts s;
+        qpp_hkdf::initial_salt_pads(s);
+        return s;
+    }();
+    return salts;
 }
 
 extern "C" {
@@ -2959,12 +2972,7 @@ int qpp_keytab_derive_initial(qpp_keytab *kt, const qpp_initial *ini, uint32_t n
             (r.slot_client == r.slot_server && !c_none))
             return QPP_E_ARG;
     }
-    // the salts' pad states: the same for every call
-    static const qpp_hkdf::InitialSalts salts = [] {
-        qpp_hkdf::InitialSalts s;
-        qpp_hkdf::initial_salt_pads(s);
-        return s;
-    }();
+    const qpp_hkdf::InitialSalts &salts = initial_salts();
     hipStream_t s = (hipStream_t)stream;
     const size_t n2 = (size_t)2 * n;
     if (n2 > kt->km_cap) {
@@ -3013,6 +3021,42 @@ int qpp_keytab_derive_initial(qpp_keytab *kt, const qpp_initial *ini, uint32_t n
     (void)hipFree(d_tmp);
     (void)hipGetLastError();
     return rc;
+}
+
+int qpp_keytab_derive_initial_device(qpp_keytab *kt, const qpp_initial *d_ini, uint32_t n,
+                                     const uint32_t *h_slots, qpp_key_material *d_km, uint8_t *d_secrets,
+                                     void *stream)
+{
+    if (!kt) return QPP_E_ARG;
+    if (n == 0) return QPP_OK;
+    if (!d_ini || !h_slots || !d_km || !d_secrets || n > (1u << 24)) return QPP_E_ARG;
+    const size_t n2 = (size_t)2 * n;
+    try {
+        // the slots the records may name: inside the table, none twice
+        std::vector<uint32_t> named;
+        named.reserve(n2);
+        for (size_t k = 0; k < n2; ++k) {
+            if (h_slots[k] == QPP_SLOT_NONE) continue;
+            if (h_slots[k] >= kt->cap) return QPP_E_ARG;
+            named.push_back(h_slots[k]);
+        }
+        std::sort(named.begin(), named.end());
+        if (std::adjacent_find(named.begin(), named.end()) != named.end()) return QPP_E_ARG;
+    } catch (...) {
+        return QPP_E_NOMEM;
+    }
+    // which of them the device installs is not known here: all are noted (an
+    // over-count only costs a later launch its single-key form, quic_pp.h)
+    for (size_t k = 0; k < n2; ++k)
+        if (h_slots[k] != QPP_SLOT_NONE) keytab_note(kt, h_slots[k], QPP_AES_128_GCM);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_derive_initial, dim3((uint32_t)((n2 + kInitialWG - 1) / kInitialWG)), dim3(kInitialWG), 0,
+                       s, d_ini, n, initial_salts(), d_km, (uint32_t *)d_secrets);
+    // not-installed directions carry QPP_SLOT_NONE >= cap: their workgroups return at once
+    hipLaunchKernelGGL(k_key_setup, dim3((uint32_t)n2), dim3(kSetupWG), 0, s, kt->d_slots, kt->d_gtab, kt->cap,
+                       d_km, (uint32_t)n2);
+    HIPCHK(hipGetLastError());
+    return QPP_OK;
 }
 
 int qpp_keytab_derive_trace(qpp_keytab *kt, int enable, float *derive_ms, float *setup_ms)

@@ -1,6 +1,7 @@
 // qpp_route.hip -- routing received datagrams to connections by connection ID
 // on the device (quic_pp.h: qpp_cidmap_*, qpp_route, qpp_route_walk,
-// qpp_session_route_unprotect, qpp_session_route_walk_unprotect).
+// qpp_route_accept, qpp_session_route_unprotect,
+// qpp_session_route_walk_unprotect, qpp_session_accept_unprotect).
 //
 // Replaces the per-datagram routing of the reference's server
 // (asyncio/server.py:60-152: pull_quic_header, then
@@ -18,6 +19,7 @@
 
 #include "quic_pp.h"
 #include "qpp_internal.h"
+#include "qpp_accept.h"
 #include "qpp_route.h"
 #include "qpp_walk.h"
 
@@ -33,6 +35,15 @@ static_assert(sizeof(qpp_walk_rec) == sizeof(qpp_wk::Rec) && QPP_WALK_MAX == qpp
               QPP_DESC_NONE == qpp_wk::kDescNone && QPP_MAX_HDR == qpp_wk::kMaxHdr &&
               QPP_W_OK == qpp_wk::kOk && QPP_W_PARSE == qpp_wk::kParse && QPP_W_HOST == qpp_wk::kHost,
               "walk records");
+static_assert(sizeof(qpp_accept_rec) == sizeof(qpp_ac::Acc) && sizeof(qpp_initial) == sizeof(qpp_ac::Initial) &&
+              sizeof(qpp_desc) == sizeof(qpp_ac::Desc) && QPP_ACC_OK == qpp_ac::kOk &&
+              QPP_ACC_ROUTED == qpp_ac::kRouted && QPP_ACC_NOT_INITIAL == qpp_ac::kNotInitial &&
+              QPP_ACC_VERSION == qpp_ac::kVersion && QPP_ACC_SMALL == qpp_ac::kSmall &&
+              QPP_ACC_CID == qpp_ac::kCid && QPP_ACC_NO_TOKEN == qpp_ac::kNoToken &&
+              QPP_A_NEED_TOKEN == qpp_ac::kNeedToken && QPP_SLOT_NONE == qpp_ac::kSlotNone &&
+              QPP_CONN_NONE == qpp_ac::kConnNone && QPP_R_LONG == qpp_ac::kClsLong &&
+              QPP_DERIVE_V2 == qpp_ac::kDeriveV2 && QPP_CID_MAX == qpp_wk::kCidMax,
+              "accept records");
 
 struct qpp_cidmap {
     HostMap host;
@@ -217,7 +228,89 @@ __global__ __launch_bounds__(kRouteWG) void k_walk(uint32_t cid_len, const uint6
     walk_n[r] = found;
 }
 
+// One lane per candidate (k_accept): the decision of
+// qpp_accept.h over the lane's own walk and route records, then its
+// qpp_initial, its accept record and, when accepted, its datagram's
+// descriptor.  No LDS, no atomics: lane a writes ini[a], acc[a] and desc[i] of
+// its own datagram i, and the rows are distinct.
+__global__ __launch_bounds__(kRouteWG) void k_accept(const uint64_t *off, const uint32_t *len, uint32_t n,
+                                                     const uint8_t *in, const qpp_route_rec *route,
+                                                     const uint32_t *long_idx, uint32_t n_long,
+                                                     const qpp_walk_rec *walk, const uint32_t *walk_n,
+                                                     const uint32_t *acc_row, const uint32_t *acc_slot,
+                                                     uint32_t n_acc, uint32_t accept_flags, uint32_t desc_flags,
+                                                     qpp_initial *ini, qpp_desc *desc, qpp_accept_rec *acc)
+{
+    const uint32_t a = blockIdx.x * kRouteWG + threadIdx.x;
+    if (a >= n_acc) return;
+    const uint32_t r = acc_row[a];
+    const uint32_t i = r < n_long ? long_idx[r] : n;
+    // a row or an index outside the batch (not the caller's contract): no
+    // record, so "not an Initial", and nothing of the batch is read
+    uint32_t conn = QPP_CONN_NONE, found = 0, l = 0;
+    uint8_t cls = QPP_R_LONG;
+    uint64_t o = 0;
+    qpp_wk::Rec w0;
+    w0.off = w0.len = w0.version = w0.desc = 0;
+    w0.pn_off = w0.token_len = 0;
+    w0.type = w0.status = w0.dcid_len = w0.scid_len = 0;
+    if (i < n) {
+        const qpp_route_rec rr = route[i];
+        conn = rr.conn;
+        cls = rr.cls;
+        found = walk_n[r];
+        o = off[i];
+        l = len[i];
+        if (found) {
+            const qpp_walk_rec q = walk[(size_t)r * QPP_WALK_MAX];
+            w0.off = q.off;
+            w0.len = q.len;
+            w0.version = q.version;
+            w0.desc = q.desc;
+            w0.pn_off = q.pn_off;
+            w0.token_len = q.token_len;
+            w0.type = q.type;
+            w0.status = q.status;
+            w0.dcid_len = q.dcid_len;
+            w0.scid_len = q.scid_len;
+        }
+    }
+    qpp_ac::Initial ri;
+    qpp_ac::Desc rd;
+    qpp_ac::Acc ra;
+    const uint8_t st = qpp_ac::accept_one(i, conn, cls, found, w0, o, l, in + o, acc_slot[2 * (size_t)a],
+                                          acc_slot[2 * (size_t)a + 1], accept_flags, (uint16_t)desc_flags, ri, rd,
+                                          ra);
+    qpp_initial qi;
+    qi.slot_client = ri.slot_client;
+    qi.slot_server = ri.slot_server;
+    qi.cid_len = ri.cid_len;
+    qi.flags = ri.flags;
+    qi.rsv[0] = qi.rsv[1] = 0;
+    for (uint32_t k = 0; k < QPP_CID_MAX; ++k) qi.cid[k] = ri.cid[k];
+    ini[a] = qi;
+    qpp_accept_rec qa;
+    qa.desc = ra.desc;
+    qa.status = ra.status;
+    qa.version = ra.version;
+    qa.rsv[0] = qa.rsv[1] = 0;
+    acc[a] = qa;
+    if (st == QPP_ACC_OK) {  // i < n: an accepted candidate has a route record
+        qpp_desc d;
+        d.in_off = rd.in_off;
+        d.out_off = rd.out_off;
+        d.len = rd.len;
+        d.hdr_len = rd.hdr_len;
+        d.flags = rd.flags;
+        d.pn = rd.pn;
+        d.slot = rd.slot;
+        d.rsv = rd.rsv;
+        desc[i] = d;
+    }
+}
+
 std::atomic<uint64_t> g_walk_launches{0};
+std::atomic<uint64_t> g_accept_launches{0};
 
 void map_entries(const qpp_cid_entry *e, uint32_t n, std::vector<HostMap::Entry> &v)
 {
@@ -386,18 +479,53 @@ int qpp_route_walk(uint32_t cid_len, const uint64_t *d_off, const uint32_t *d_le
 
 uint64_t qpp_route_walk_launches(void) { return g_walk_launches.load(std::memory_order_relaxed); }
 
-// Both session forms.  walk_form: conn_slot / conn_expected are the walk's
+int qpp_route_accept(const uint64_t *d_off, const uint32_t *d_len, uint32_t n, const uint8_t *d_in,
+                     const qpp_route_rec *d_route, const uint32_t *d_long_idx, uint32_t n_long,
+                     const qpp_walk_rec *d_walk, const uint32_t *d_walk_n, const uint32_t *d_acc_row,
+                     const uint32_t *d_acc_slot, uint32_t n_acc, uint32_t accept_flags, uint16_t desc_flags,
+                     qpp_initial *d_ini, qpp_desc *d_desc, qpp_accept_rec *d_acc, void *stream)
+{
+    if (accept_flags & ~QPP_A_NEED_TOKEN) return QPP_E_ARG;
+    if (n_acc == 0) return QPP_OK;
+    if (!d_off || !d_len || !d_in || !d_route || !d_long_idx || !d_walk || !d_walk_n || !d_acc_row || !d_acc_slot ||
+        !d_ini || !d_desc || !d_acc)
+        return QPP_E_ARG;
+    hipLaunchKernelGGL(k_accept, dim3((n_acc + kRouteWG - 1) / kRouteWG), dim3(kRouteWG), 0, (hipStream_t)stream,
+                       d_off, d_len, n, d_in, d_route, d_long_idx, n_long, d_walk, d_walk_n, d_acc_row, d_acc_slot,
+                       n_acc, accept_flags, (uint32_t)desc_flags, d_ini, d_desc, d_acc);
+    HIPCHK(hipGetLastError());
+    g_accept_launches.fetch_add(1, std::memory_order_relaxed);
+    return QPP_OK;
+}
+
+uint64_t qpp_route_accept_launches(void) { return g_accept_launches.load(std::memory_order_relaxed); }
+
+// The new-connection step of qpp_session_accept_unprotect.
+struct AcceptArgs {
+    qpp_keytab *kt;
+    const uint32_t *row, *slot;
+    uint32_t n, flags;
+    qpp_accept_rec *acc_out;
+    qpp_key_material *km_out;
+    uint8_t *secrets_out;
+};
+
+// The session forms.  walk_form: conn_slot / conn_expected are the walk's
 // per-key-set and per-space arrays, and the routing kernel's per-connection
 // ones (the 1-RTT slot, the application space's number) are taken from them.
+// ac (walk form only; NULL or no candidates: nothing of it happens): the
+// accepting kernel and the key derivation between the walk and the unprotect.
 static int route_unprotect(qpp_session *s, const qpp_keytab *kt, const qpp_cidmap *m, uint32_t cid_len,
                            const uint64_t *off, const uint32_t *len, uint32_t n, const uint8_t *in, size_t in_len,
                            bool walk_form, const uint32_t *long_idx, uint32_t n_long, const uint32_t *conn_slot,
                            const uint64_t *conn_expected, uint32_t n_conn, uint16_t desc_flags, uint8_t *out,
                            size_t out_len, qpp_desc *desc_out, qpp_route_rec *route_out, qpp_result *res,
-                           qpp_walk_rec *walk_out, uint32_t *walk_n_out)
+                           qpp_walk_rec *walk_out, uint32_t *walk_n_out, const AcceptArgs *ac = NULL)
 {
     if (!s || !kt || !m || cid_len < 1 || cid_len > QPP_CID_MAX) return QPP_E_ARG;
-    if (n == 0) return n_long ? QPP_E_ARG : QPP_OK;
+    const uint32_t n_acc = ac ? ac->n : 0;
+    if (ac && (ac->flags & ~QPP_A_NEED_TOKEN)) return QPP_E_ARG;
+    if (n == 0) return n_long || n_acc ? QPP_E_ARG : QPP_OK;
     if (!off || !len || !route_out || !res || (in_len && !in) || (out_len && !out) ||
         (n_conn && (!conn_slot || !conn_expected)))
         return QPP_E_ARG;
@@ -409,6 +537,27 @@ static int route_unprotect(qpp_session *s, const qpp_keytab *kt, const qpp_cidma
             return QPP_E_ARG;
     for (uint32_t r = 0; r < n_long; ++r)
         if (long_idx[r] >= n || (r && long_idx[r] <= long_idx[r - 1])) return QPP_E_ARG;
+    if (n_acc) {
+        if (!ac->row || !ac->slot || !ac->acc_out || !ac->km_out || !ac->secrets_out || n_acc > (1u << 24))
+            return QPP_E_ARG;
+        const uint32_t cap = qpp_keytab_capacity(kt);
+        for (uint32_t a = 0; a < n_acc; ++a)
+            if (ac->row[a] >= n_long || (a && ac->row[a] <= ac->row[a - 1]) || ac->slot[2 * (size_t)a] >= cap ||
+                (ac->slot[2 * (size_t)a + 1] >= cap && ac->slot[2 * (size_t)a + 1] != QPP_SLOT_NONE))
+                return QPP_E_ARG;
+        // pairwise distinct, checked here too: a refusal by
+        // qpp_keytab_derive_initial_device would come after the first kernels
+        try {
+            std::vector<uint32_t> named;
+            named.reserve(2 * (size_t)n_acc);
+            for (size_t k = 0; k < 2 * (size_t)n_acc; ++k)
+                if (ac->slot[k] != QPP_SLOT_NONE) named.push_back(ac->slot[k]);
+            std::sort(named.begin(), named.end());
+            if (std::adjacent_find(named.begin(), named.end()) != named.end()) return QPP_E_ARG;
+        } catch (...) {
+            return QPP_E_NOMEM;
+        }
+    }
     const uint32_t nd = n + 3u * n_long;  // descriptors and results
     // scratch: [off | len | conn_slot | conn_expected | long_idx | key-set slots | space numbers]
     // go up in one copy, [desc | route | results | walk records | walk counts] come back in one
@@ -416,15 +565,22 @@ static int route_unprotect(qpp_session *s, const qpp_keytab *kt, const qpp_cidma
                  o_exp = o_slot + al256((size_t)n_conn * 4), o_long = o_exp + al256((size_t)n_conn * 8),
                  o_kslot = o_long + (n_long ? al256((size_t)n_long * 4) : 0),
                  o_kexp = o_kslot + (n_long ? al256((size_t)n_conn * QPP_KEYSETS * 4) : 0),
-                 up = o_kexp + (n_long ? al256((size_t)n_conn * QPP_SPACES * 8) : 0);
+                 o_arow = o_kexp + (n_long ? al256((size_t)n_conn * QPP_SPACES * 8) : 0),
+                 o_aslot = o_arow + (n_acc ? al256((size_t)n_acc * 4) : 0),
+                 up = o_aslot + (n_acc ? al256((size_t)n_acc * 8) : 0);
     const size_t o_route = al256((size_t)nd * sizeof(qpp_desc)),
                  o_res = o_route + al256((size_t)n * sizeof(qpp_route_rec)),
                  o_walk = o_res + al256((size_t)nd * sizeof(qpp_result)),
                  o_walkn = o_walk + (n_long ? al256((size_t)n_long * QPP_WALK_MAX * sizeof(qpp_walk_rec)) : 0),
-                 down = o_walkn + (n_long ? al256((size_t)n_long * 4) : 0);
+                 o_acc = o_walkn + (n_long ? al256((size_t)n_long * 4) : 0),
+                 o_km = o_acc + (n_acc ? al256((size_t)n_acc * sizeof(qpp_accept_rec)) : 0),
+                 o_sec = o_km + (n_acc ? al256((size_t)n_acc * 2 * sizeof(qpp_key_material)) : 0),
+                 down = o_sec + (n_acc ? al256((size_t)n_acc * 64) : 0);
+    // the candidates' qpp_initial records never leave the device: scratch past both copies
+    const size_t ini_bytes = n_acc ? al256((size_t)n_acc * sizeof(qpp_initial)) : 0;
     qpp_session_bufs b;
     const size_t need = in_len > out_len ? in_len : out_len;
-    int rc = qpp_internal_session_bufs(s, need, nd, up + down, &b);
+    int rc = qpp_internal_session_bufs(s, need, nd, up + down + ini_bytes, &b);
     if (rc != QPP_OK) return rc;
     uint8_t *hu = b.h_scratch, *du = b.d_scratch, *hd = b.h_scratch + up, *dd = b.d_scratch + up;
     memcpy(hu, off, (size_t)n * 8);
@@ -447,6 +603,10 @@ static int route_unprotect(qpp_session *s, const qpp_keytab *kt, const qpp_cidma
             memcpy(hu + o_kexp, conn_expected, (size_t)n_conn * QPP_SPACES * 8);
         }
     }
+    if (n_acc) {
+        memcpy(hu + o_arow, ac->row, (size_t)n_acc * 4);
+        memcpy(hu + o_aslot, ac->slot, (size_t)n_acc * 8);
+    }
     if (in_len && in != b.h_in) memcpy(b.h_in, in, in_len);  // staged by the caller already?
     HIPCHK(hipMemcpyAsync(du, hu, up, hipMemcpyHostToDevice, b.stream));
     if (in_len) HIPCHK(hipMemcpyAsync(b.d_in, b.h_in, in_len, hipMemcpyHostToDevice, b.stream));
@@ -466,6 +626,20 @@ static int route_unprotect(qpp_session *s, const qpp_keytab *kt, const qpp_cidma
                             (qpp_walk_rec *)(dd + o_walk), (uint32_t *)(dd + o_walkn), b.stream);
         if (rc != QPP_OK) return rc;
     }
+    if (n_acc) {
+        qpp_initial *d_ini = (qpp_initial *)(dd + down);
+        rc = qpp_route_accept((const uint64_t *)du, (const uint32_t *)(du + o_len), n, b.d_in, d_route,
+                              (const uint32_t *)(du + o_long), n_long, (const qpp_walk_rec *)(dd + o_walk),
+                              (const uint32_t *)(dd + o_walkn), (const uint32_t *)(du + o_arow),
+                              (const uint32_t *)(du + o_aslot), n_acc, ac->flags, desc_flags, d_ini, d_desc,
+                              (qpp_accept_rec *)(dd + o_acc), b.stream);
+        if (rc != QPP_OK) return rc;
+        // notes every candidate's slots in the table's bookkeeping before the
+        // unprotect launch below chooses its kernel form from it
+        rc = qpp_keytab_derive_initial_device(ac->kt, d_ini, n_acc, ac->slot, (qpp_key_material *)(dd + o_km),
+                                              dd + o_sec, b.stream);
+        if (rc != QPP_OK) return rc;
+    }
     rc = qpp_unprotect(kt, d_desc, nd, b.d_in, b.d_out, d_res, b.stream);
     if (rc != QPP_OK) return rc;
     if (out_len) HIPCHK(hipMemcpyAsync(b.h_out, b.d_out, out_len, hipMemcpyDeviceToHost, b.stream));
@@ -478,6 +652,11 @@ static int route_unprotect(qpp_session *s, const qpp_keytab *kt, const qpp_cidma
     if (n_long) {
         memcpy(walk_out, hd + o_walk, (size_t)n_long * QPP_WALK_MAX * sizeof(qpp_walk_rec));
         memcpy(walk_n_out, hd + o_walkn, (size_t)n_long * 4);
+    }
+    if (n_acc) {
+        memcpy(ac->acc_out, hd + o_acc, (size_t)n_acc * sizeof(qpp_accept_rec));
+        memcpy(ac->km_out, hd + o_km, (size_t)n_acc * 2 * sizeof(qpp_key_material));
+        memcpy(ac->secrets_out, hd + o_sec, (size_t)n_acc * 64);
     }
     return QPP_OK;
 }
@@ -514,6 +693,22 @@ int qpp_session_route_walk_unprotect(qpp_session *s, const qpp_keytab *kt, const
     return settle(s, route_unprotect(s, kt, m, cid_len, off, len, n, in, in_len, true, long_idx, n_long, conn_slot,
                                      conn_expected, n_conn, desc_flags, out, out_len, desc_out, route_out, res,
                                      walk_out, walk_n_out));
+}
+
+int qpp_session_accept_unprotect(qpp_session *s, qpp_keytab *kt, const qpp_cidmap *m, uint32_t cid_len,
+                                 const uint64_t *off, const uint32_t *len, uint32_t n, const uint8_t *in,
+                                 size_t in_len, const uint32_t *long_idx, uint32_t n_long,
+                                 const uint32_t *conn_slot, const uint64_t *conn_expected, uint32_t n_conn,
+                                 uint16_t desc_flags, const uint32_t *acc_row, const uint32_t *acc_slot,
+                                 uint32_t n_acc, uint32_t accept_flags, uint8_t *out, size_t out_len,
+                                 qpp_desc *desc_out, qpp_route_rec *route_out, qpp_result *res,
+                                 qpp_walk_rec *walk_out, uint32_t *walk_n_out, qpp_accept_rec *acc_out,
+                                 qpp_key_material *km_out, uint8_t *secrets_out)
+{
+    const AcceptArgs ac = {kt, acc_row, acc_slot, n_acc, accept_flags, acc_out, km_out, secrets_out};
+    return settle(s, route_unprotect(s, kt, m, cid_len, off, len, n, in, in_len, true, long_idx, n_long, conn_slot,
+                                     conn_expected, n_conn, desc_flags, out, out_len, desc_out, route_out, res,
+                                     walk_out, walk_n_out, &ac));
 }
 
 }  // extern "C"

@@ -92,8 +92,14 @@ KEYSETS = 5    # QPP_KEYSETS: Initial v1, Initial v2, 0-RTT, Handshake, 1-RTT
 SPACES = 3     # QPP_SPACES: Initial, Handshake, application
 DESC_NONE = 0xFFFFFFFF
 W_OK, W_PARSE, W_HOST = 0, 1, 2
+# qpp_accept_rec: the device's verdict on one candidate of qpp_route_accept (an
+# unrouted Initial a server may answer): its datagram (= packet 0's descriptor)
+# or DESC_NONE, an ACC_* status, and 0 / 1 for QUIC version 1 / 2
+ACCEPT = np.dtype([("desc", "<u4"), ("status", "u1"), ("version", "u1"), ("rsv", "u1", (2,))])
+ACC_OK, ACC_ROUTED, ACC_NOT_INITIAL, ACC_VERSION, ACC_SMALL, ACC_CID, ACC_NO_TOKEN = 0, 1, 2, 3, 4, 5, 6
+A_NEED_TOKEN = 1  # QPP_A_NEED_TOKEN: the server's Retry mode, an Initial must carry a token
 assert DESC.itemsize == 40 and RESULT.itemsize == 16 and KEY_MATERIAL.itemsize == 84
-assert WALK.itemsize == 24
+assert WALK.itemsize == 24 and ACCEPT.itemsize == 8
 assert SECRET.itemsize == 80 and INITIAL.itemsize == 32
 assert CID_ENTRY.itemsize == 32 and ROUTE.itemsize == 8
 

@@ -42,7 +42,8 @@ import numpy as np
 from . import _crypto
 from . import layout as L
 from ._crypto import CryptoError
-from .batch_io import ConnectionClosedError, ReceiveBatch, ReservedBitsError, default_slots
+from .batch_io import (ConnectionClosedError, ReceiveBatch, ReservedBitsError, _initial_directions, _install_initial,
+                       default_slots, setup_initial_batch)
 from .buffer import Buffer
 from .crypto import KeyUnavailableError
 from .packet import (
@@ -360,7 +361,22 @@ def _keysets(conn: ConnectionKeys) -> tuple:
             conn.cryptos.get(Epoch.HANDSHAKE))
 
 
-def _routed_long(conns, datagrams, cid_len: int, idx: list, cls, rconn, longs, slots) -> Optional[list]:
+def _long_header(data: bytes, start: int, ptype, version: int, length: int, dl: int, sl: int, tok: int) -> QuicHeader:
+    """The QuicHeader of a packet-protected long-header packet from its walk
+    record's fields (qpp_walk_rec): the CIDs and the token are cut out of the
+    datagram, nothing is parsed again."""
+    at = start + 6 + dl
+    dcid, scid = data[start + 6:at], data[at + 1:at + 1 + sl]
+    token = b""
+    if ptype == QuicPacketType.INITIAL:
+        at += 1 + sl
+        at += 1 << (data[at] >> 6)  # the token length's own bytes
+        token = data[at:at + tok]
+    return QuicHeader(version, ptype, length, dcid, scid, token=token)
+
+
+def _routed_long(conns, datagrams, cid_len: int, idx: list, cls, rconn, longs, slots,
+                 accepted: Optional[dict] = None) -> Optional[list]:
     """receive_routed for a batch with long headers to known connections,
     from what the fused call returned (_crypto.receive_routed): the device
     has parsed every listed datagram (qpp_walk_rec) and unprotected every
@@ -371,7 +387,15 @@ def _routed_long(conns, datagrams, cid_len: int, idx: list, cls, rconn, longs, s
     defers (key-phase flips, stale expected numbers) is launched again.
     None, with no state touched: a datagram the device left to the host walk,
     or an Initial the device had no key-set for; the caller's general path
-    takes the batch."""
+    takes the batch.
+    `accepted` (accept_routed): {datagram: its new connection} for the
+    datagrams the device accepted in the same call; `idx` lists them among the
+    routed ones.  Packet 0 of such a datagram was unprotected by the fused
+    launch with the connection's fresh Initial keys (its descriptor is the
+    datagram's); its later packets had no descriptor, so they run in a second
+    ReceiveBatch after the first, in order, with whatever keys the connection
+    has by then."""
+    accepted = accepted or {}
     lidx_b, walk_b, wn_b, desc_b, res_b, out_b = longs
     row_of = {i: r for r, i in enumerate(np.frombuffer(lidx_b, np.uint32).tolist())}
     walk = np.frombuffer(walk_b, dtype=L.WALK).reshape(-1, L.WALK_MAX)
@@ -386,11 +410,13 @@ def _routed_long(conns, datagrams, cid_len: int, idx: list, cls, rconn, longs, s
     out: list = []
     queued: list = []
     pairs, packets, offs, spaces, pconns, rsvs, dix = [], [], [], [], [], [], []
+    late: list = []  # packets after packet 0 of accepted datagrams: (queue entry, add() arguments)
     items = {}
     by_conn: dict = {}
     r_short = L.R_SHORT
     for i in idx:
-        conn = conns[rconn[i]]
+        fresh = i in accepted
+        conn = accepted[i] if fresh else conns[rconn[i]]
         data = datagrams[i]
         items[i] = (conn, data)
         if conn.closed:
@@ -424,14 +450,8 @@ def _routed_long(conns, datagrams, cid_len: int, idx: list, cls, rconn, longs, s
             elif ptype == one_rtt:
                 header = QuicHeader(None, one_rtt, w_len[r][k], data[start + 1:start + 1 + cid_len], b"")
             else:
-                at = start + 6 + w_dl[r][k]
-                dcid, scid = data[start + 6:at], data[at + 1:at + 1 + w_sl[r][k]]
-                token = b""
-                if ptype == initial:
-                    at += 1 + w_sl[r][k]
-                    at += 1 << (data[at] >> 6)  # the token length's own bytes
-                    token = data[at:at + w_tok[r][k]]
-                header = QuicHeader(w_ver[r][k], ptype, w_len[r][k], dcid, scid, token=token)
+                header = _long_header(data, start, ptype, w_ver[r][k], w_len[r][k], w_dl[r][k], w_sl[r][k],
+                                      w_tok[r][k])
             if not conn.is_client and ptype == initial and len(data) < SMALLEST_MAX_DATAGRAM_SIZE:
                 out.append(ReceivedPacket(i, start, header, ptype, Epoch.INITIAL,
                                           dropped="initial_packet_datagram_too_small"))
@@ -453,15 +473,34 @@ def _routed_long(conns, datagrams, cid_len: int, idx: list, cls, rconn, longs, s
             if ptype == initial and header.version not in (_V1, _V2) and pair is not None \
                     and pair.recv.aead is not None:
                 return None  # keys the device had no key-set for
+            rsv = _RSV_SHORT if ptype == one_rtt else _RSV_LONG
+            if fresh and k:
+                late.append(((len(out), (i, start, header, ptype, epoch)),
+                             (pair, data[start:start + w_len[r][k]], w_pn[r][k], space, conn, rsv)))
+                out.append(None)
+                continue
             queued.append((len(out), (i, start, header, ptype, epoch)))
             out.append(None)
             pairs.append(pair), packets.append(data[start:start + w_len[r][k]]), offs.append(w_pn[r][k])
             spaces.append(space), pconns.append(conn)
-            rsvs.append(_RSV_SHORT if ptype == one_rtt else _RSV_LONG), dix.append(w_desc[r][k])
+            rsvs.append(rsv), dix.append(i if fresh else w_desc[r][k])
     rb = ReceiveBatch(slots=slots)
     rb._extend(pairs, packets, offs, spaces, pconns, rsvs)
     rb.preset(desc_b, res_b, dix, out_b)
-    return _finish(items, out, queued, rb.run())
+    results = rb.run()
+    if late:
+        # a connection the first walk closed ignores what follows (connection.py:756-757)
+        shut = {id(c) for c, res in zip(pconns, results) if isinstance(res, ReservedBitsError)}
+        rb = ReceiveBatch(slots=slots)
+        todo = [(q, a) for q, a in late if id(a[4]) not in shut and a[0] is not None]
+        for _, (pair, packet, off, space, conn, rsv) in todo:
+            rb.add(pair, packet, off, space=space, conn=conn, reserved_mask=rsv)
+        got = dict(zip((q[0] for q, _ in todo), rb.run()))
+        for q, a in late:
+            queued.append(q)
+            results.append(got.get(q[0], KeyUnavailableError("Decryption key is not available") if a[0] is None
+                                   else ConnectionClosedError("Connection is closed")))
+    return _finish(items, out, queued, results)
 
 
 def receive_routed(router, datagrams: Sequence[bytes]) -> Tuple[List[ReceivedPacket], List[Tuple[int, int]]]:
@@ -500,6 +539,21 @@ def receive_routed(router, datagrams: Sequence[bytes]) -> Tuple[List[ReceivedPac
         return [], []
     conns = router.conns
     general = any(c is not None and c.is_client and c.host_cids is not None for c in conns)
+    slots, uspaces, sexp, arrays, _ = _routed_arrays(router, datagrams, general)
+    route_b, walked, longs = _crypto.receive_routed(
+        slots.table, router.map, router.host_cid_length, datagrams, *arrays, ReceivedPacket,
+        QuicPacketType.ONE_RTT, Epoch.ONE_RTT, bytes(bool(c is not None and c.closed) for c in conns),
+        0 if general else 1)
+    return _routed_finish(router, datagrams, slots, uspaces, sexp, route_b, walked, longs)
+
+
+def _routed_arrays(router, datagrams: list, general: bool):
+    """What the fused calls of receive_routed and accept_routed take besides
+    the datagrams: every key the batch can need is given a slot here, in one
+    assign().  Returns (slots, the distinct 1-RTT spaces, their expected
+    numbers, the packed per-connection arrays in _crypto.receive_routed's
+    order, the DCIDs of the batch's long headers or None)."""
+    conns = router.conns
     pix: dict = {}
     six: dict = {}
     upairs, uspaces, c_pair, c_space = [], [], [], []
@@ -574,11 +628,13 @@ def receive_routed(router, datagrams: Sequence[bytes]) -> Tuple[List[ReceivedPac
                 if e in sp:
                     ke_arr[c, j] = sp[e].expected_packet_number & 0xFFFFFFFFFFFFFFFF
         kslot, kexp = ks_arr.tobytes(), ke_arr.tobytes()
-    route_b, walked, longs = _crypto.receive_routed(
-        slots.table, router.map, router.host_cid_length, datagrams, a_pair.astype(np.uint32).tobytes(),
-        a_space.astype(np.uint32).tobytes(), pslot.tobytes(), sexp.tobytes(), kslot, kexp, ReceivedPacket,
-        QuicPacketType.ONE_RTT, Epoch.ONE_RTT, bytes(bool(c is not None and c.closed) for c in conns),
-        0 if general else 1)
+    return slots, uspaces, sexp, (a_pair.astype(np.uint32).tobytes(), a_space.astype(np.uint32).tobytes(),
+                                  pslot.tobytes(), sexp.tobytes(), kslot, kexp), dcids
+
+
+def _routed_finish(router, datagrams: list, slots, uspaces, sexp, route_b, walked, longs):
+    """receive_routed from what its fused call returned."""
+    conns = router.conns
     route = np.frombuffer(route_b, dtype=L.ROUTE)
     cls, rconn = route["cls"], route["conn"]
     routed = ((cls == L.R_SHORT) | (cls == L.R_LONG)) & (rconn != L.CONN_NONE)
@@ -613,3 +669,150 @@ def receive_routed(router, datagrams: Sequence[bytes]) -> Tuple[List[ReceivedPac
             if isinstance(res, ReservedBitsError):
                 conns[rconn[at[j]]].closed = True
     return recs, unrouted
+
+
+def _host_walk_needed(conns, rconn, lidx: list, walk, wn: list) -> bool:
+    """_routed_long's two reasons to leave a batch to the general path, asked
+    before any state is touched: a datagram the device left to the host walk,
+    or a known connection's keyed Initial of a version that is neither 1 nor 2."""
+    live = np.arange(L.WALK_MAX)[None, :] < np.asarray(wn, np.int64)[:, None]
+    if ((walk["status"] == L.W_HOST) & live).any():
+        return True
+    odd = live & (walk["status"] == L.W_OK) & (walk["type"] == QuicPacketType.INITIAL.value) \
+        & (walk["version"] != int(_V1)) & (walk["version"] != int(_V2))
+    for r, k in zip(*np.nonzero(odd)):
+        c = int(rconn[lidx[r]])
+        if c == L.CONN_NONE or c >= len(conns) or conns[c] is None or conns[c].closed:
+            continue
+        pair, _ = conns[c].pair_and_space(Epoch.INITIAL, int(walk["version"][r, k]))
+        if pair is not None and pair.recv.aead is not None:
+            return True
+    return False
+
+
+def accept_routed(router, datagrams: Sequence[bytes], accept, *, need_token: bool = False):
+    """receive_routed for a server that also takes on new connections.
+
+    Returns (records, unrouted, accepted).  The first datagrams of a new
+    connection no longer stop in `unrouted`: in the same fused call that
+    routes, walks and unprotects the batch (_crypto.receive_accept), the
+    device looks at the walk record of every long-header datagram whose DCID
+    the router does not know, decides whether a server may answer it (an
+    Initial of version 1 or 2 at the datagram's start, a datagram of at least
+    1200 bytes, a DCID of 1..20 bytes and, with `need_token`, a token: the
+    checks of asyncio/server.py:60-152), derives the Initial keys of those it
+    accepts from their DCIDs, installs them and unprotects their first packet.
+    Nothing is parsed on the host and the bytes are uploaded once.
+
+    The host then decides policy with the header in hand.  For the first
+    device-accepted datagram of each distinct DCID, in datagram order,
+    `accept(header, datagram_index)` returns the new connection: a server's
+    ConnectionKeys of the router's host CID length whose
+    cryptos_initial[header.version] is an unset pair and whose Initial space
+    expects packet number 0 (ValueError otherwise), or None to refuse; a
+    refused datagram, and every later one of its DCID, goes to `unrouted`.
+    `accept` runs before the new keys are bound to their slots, so it must not
+    protect or unprotect packets itself; it may add the connection's host CIDs
+    to the router (server.py:149).  An accepted connection's pair ends exactly
+    as pair.setup_initial(dcid, is_client=False, version) leaves it, its two
+    slots are bound to its keys, it enters the router under the original DCID
+    (server.py:148), and the pairs of its other supported versions get their
+    keys from one setup_initial_batch call over all accepted connections
+    (connection.py:1509-1515).  The accepted datagrams then join the routed
+    ones in the policy pass and the in-order walk, packet 0 from the fused
+    launch's results; `accepted` is [(datagram_index, connection)], one entry
+    per new connection.
+
+    Candidates are taken in datagram order and cut to the key slots left
+    after the batch's own keys were assigned, two per candidate: the table is
+    never cleared and refilled on their account, and the candidates cut come
+    back in `unrouted`, as from receive_routed.  The same keys are derived
+    once per datagram of a DCID on purpose (no cross-lane dedupe on the
+    device); the slots nothing adopted -- of candidates the device rejected,
+    of refused ones, of second and later datagrams of one DCID -- are cleared
+    in one KeyTable.clear and free again when the call returns.
+
+    A batch that receive_routed would leave to its general path (a datagram
+    the device leaves to the host walk, and so on) goes through
+    receive_routed, and nothing is accepted.  ValueError for a router that
+    holds a client connection checking its host CIDs."""
+    datagrams = datagrams if isinstance(datagrams, list) else list(datagrams)
+    if not datagrams:
+        return [], [], []
+    conns = router.conns
+    if any(c is not None and c.is_client and c.host_cids is not None for c in conns):
+        raise ValueError("accept_routed is a server's: the router holds a client connection")
+    cid_len = router.host_cid_length
+    slots, _, _, arrays, dcids = _routed_arrays(router, datagrams, False)
+    # the rows of the device walk as _crypto lists them: first byte, bit 7
+    first = np.fromiter((d[0] if d else 0 for d in datagrams), np.uint8, len(datagrams))
+    lidx = np.flatnonzero(first & PACKET_LONG_HEADER).tolist()
+    rows, cand = [], []
+    if dcids is not None:
+        for r, i in enumerate(lidx):
+            d = datagrams[i]
+            if len(d) >= 6 and d[5] <= L.CID_MAX and len(d) >= 6 + d[5] and router.index_of(d[6:6 + d[5]]) is None:
+                rows.append(r), cand.append(i)
+        keep = min(len(cand), slots.room() // 2)
+        rows, cand = rows[:keep], cand[:keep]
+    if not cand:
+        return receive_routed(router, datagrams) + ([],)
+    taken = slots.reserve(2 * len(cand))  # inside room(): no refill
+    try:
+        route_b, _, longs, found = _crypto.receive_accept(
+            slots.table, router.map, cid_len, datagrams, *arrays, ReceivedPacket, QuicPacketType.ONE_RTT,
+            Epoch.ONE_RTT, bytes(bool(c is not None and c.closed) for c in conns), 1,
+            np.asarray(rows, np.uint32).tobytes(), np.asarray(taken, np.uint32).tobytes(),
+            L.A_NEED_TOKEN if need_token else 0)
+        route = np.frombuffer(route_b, dtype=L.ROUTE)
+        cls, rconn = route["cls"], route["conn"]
+        walk = np.frombuffer(longs[1], dtype=L.WALK).reshape(-1, L.WALK_MAX)
+        wn = np.frombuffer(longs[2], np.uint32).tolist()
+        host = _host_walk_needed(conns, rconn, lidx, walk, wn)
+        acc = np.frombuffer(found[0], dtype=L.ACCEPT)
+        km = np.frombuffer(found[1], dtype=L.KEY_MATERIAL)
+        by_dcid: dict = {}  # DCID -> its connection, or None once refused
+        joined: dict = {}   # datagram -> connection
+        new: list = []      # (datagram, connection, candidate, header) per new connection
+        for a in () if host else np.flatnonzero(acc["status"] == L.ACC_OK).tolist():
+            i, w = cand[a], walk[rows[a], 0]
+            data = datagrams[i]
+            dcid = data[6:6 + int(w["dcid_len"])]
+            if dcid not in by_dcid:
+                header = _long_header(data, 0, QuicPacketType.INITIAL, int(w["version"]), int(w["len"]),
+                                      int(w["dcid_len"]), int(w["scid_len"]), int(w["token_len"]))
+                conn = by_dcid[dcid] = accept(header, i)
+                if conn is not None:
+                    pair = (conn.cryptos_initial or {}).get(header.version)
+                    space = conn.spaces.get(Epoch.INITIAL)
+                    if conn.is_client or conn.host_cid_length != cid_len or pair is None \
+                            or pair.recv.aead is not None or pair.send.aead is not None:
+                        raise ValueError("accept() must return a server connection of the router's host CID length "
+                                         "whose Initial pair of the header's version is unset")
+                    if space is None or space.expected_packet_number != 0:
+                        raise ValueError("accept() must return a connection whose Initial space expects packet 0")
+                    new.append((i, conn, a, header))
+            if by_dcid[dcid] is not None:
+                joined[i] = by_dcid[dcid]
+        # the new connections' keys are on the device already: bind their slots, free the rest
+        built = [_initial_directions(km, found[2], a, False) for _, _, a, _ in new]
+        _install_initial(slots, [c.cryptos_initial[h.version] for _, c, _, h in new], built,
+                         [h.version for _, _, _, h in new])
+    finally:
+        slots.give_back(taken)
+    if host:
+        return receive_routed(router, datagrams) + ([],)
+    others = [(c.cryptos_initial[v], h.destination_cid, v) for _, c, _, h in new for v in c.supported_versions
+              if v != h.version and v in c.cryptos_initial and c.cryptos_initial[v].recv.aead is None]
+    if others:
+        setup_initial_batch([o[0] for o in others], [o[1] for o in others], False, [o[2] for o in others], slots)
+    for _, conn, _, header in new:
+        router.add(header.destination_cid, conn)  # server.py:148
+    routed = ((cls == L.R_SHORT) | (cls == L.R_LONG)) & (rconn != L.CONN_NONE)
+    here = routed.copy()
+    here[np.asarray(list(joined), np.int64)] = True
+    unrouted = [(int(i), int(cls[i])) for i in np.flatnonzero(~here)]
+    recs = _routed_long(router.conns, datagrams, cid_len, np.flatnonzero(here).tolist(), cls, rconn, longs, slots,
+                        joined)
+    assert recs is not None  # _host_walk_needed ruled its reasons out
+    return recs, unrouted, [(i, c) for i, c, _, _ in new]

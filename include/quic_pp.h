@@ -228,6 +228,33 @@ int qpp_keytab_derive(qpp_keytab *kt, const qpp_secret *sec, uint32_t n,
  * Synchronous, like qpp_keytab_derive: the records are caller memory. */
 int qpp_keytab_derive_initial(qpp_keytab *kt, const qpp_initial *ini, uint32_t n,
                               qpp_key_material *km_out, uint8_t *secrets_out, void *stream);
+/* qpp_keytab_derive_initial over n records that already lie in device memory
+ * (d_ini, e.g. written by qpp_route_accept earlier on the same stream).
+ * Asynchronous on `stream`: no allocation and no synchronisation inside.  It
+ * launches the same two kernels as qpp_keytab_derive_initial, the derivation
+ * and then the slot expansion, with the same grids.  d_km (2n
+ * qpp_key_material) and d_secrets (2n x 32 bytes) are caller-owned device
+ * buffers that receive what km_out / secrets_out receive there, in the same
+ * order; both are required.
+ * The host cannot know which records the device will install, so h_slots[2n]
+ * (host memory) lists the slots the records may name, QPP_SLOT_NONE entries
+ * skipped.  Every listed slot is noted as QPP_AES_128_GCM in the table's host
+ * bookkeeping before the launch.  Listing a slot that no record installs (an
+ * over-count) only makes a later launch choose the general AES-GCM kernel
+ * form over the single-key forms; the general form is correct for any number
+ * of keys.  Not listing a slot that a record installs (an under-count) is not
+ * safe.  The caller clears the listed slots that were not installed with
+ * qpp_keytab_clear afterwards, which also takes them out of the bookkeeping.
+ * QPP_E_ARG, with nothing launched or noted: NULL kt, a NULL array with n > 0,
+ * n > 2^24, a listed slot >= capacity that is not QPP_SLOT_NONE, the same
+ * slot listed twice.  n == 0 returns QPP_OK.  The records' own fields are the
+ * device's: a slot >= capacity in one is skipped by the slot expansion, a
+ * cid_len > QPP_CID_MAX is the caller's to rule out (qpp_route_accept never
+ * writes one).  The timing of qpp_keytab_derive_trace does not cover this
+ * call. */
+int qpp_keytab_derive_initial_device(qpp_keytab *kt, const qpp_initial *d_ini, uint32_t n,
+                                     const uint32_t *h_slots, qpp_key_material *d_km, uint8_t *d_secrets,
+                                     void *stream);
 /* Where a qpp_keytab_derive_initial call's device time goes (diagnostic, for
  * tools/bench_initial_keys.py): enable != 0 makes the table's following calls
  * put timing events around their two kernels (0 off, -1 unchanged); derive_ms
@@ -440,6 +467,75 @@ int qpp_route_walk(uint32_t cid_len, const uint64_t *d_off, const uint32_t *d_le
  * library loaded).  Diagnostic: an all-short batch makes none. */
 uint64_t qpp_route_walk_launches(void);
 
+/* qpp_route_accept: the unrouted Initials of a routed and walked batch that a
+ * server may answer (asyncio/server.py:60-152, the checks it runs before it
+ * creates a connection), with the record their Initial keys are derived from
+ * and the descriptor their first packet is unprotected with.  Asynchronous
+ * on `stream`; runs after qpp_route and qpp_route_walk on the same stream,
+ * over the same datagram arrays and the d_route, d_long_idx, d_walk and
+ * d_walk_n of those calls (all read only here) and their d_desc.
+ * d_acc_row[n_acc] names the candidates: strictly increasing rows r <
+ * n_long of the walk's listing, so the datagram is i = d_long_idx[r] (the
+ * caller's to guarantee for this device form; a row >= n_long, or an index
+ * >= n, reads nothing of the batch and is QPP_ACC_NOT_INITIAL).
+ * d_acc_slot[2 n_acc] gives two key slots per candidate: [2a] for the "client
+ * in" keys (the server's receive direction) and [2a + 1] for the "server in"
+ * keys, which may be QPP_SLOT_NONE.  One lane per candidate.  Lane a accepts
+ * its datagram if and only if all of these hold; the first that fails gives
+ * d_acc[a].status:
+ *   1. d_route[i] is (QPP_CONN_NONE, QPP_R_LONG)              QPP_ACC_ROUTED
+ *   2. d_walk_n[r] >= 1 and packet 0's record is QPP_W_OK, of type Initial,
+ *      at offset 0 (so not a parse error, QPP_W_HOST, Version Negotiation,
+ *      Retry, or Handshake / 0-RTT to an unknown DCID)        QPP_ACC_NOT_INITIAL
+ *   3. the version is 1 or 2 (version negotiation is the host's,
+ *      server.py:71-84)                                       QPP_ACC_VERSION
+ *   4. d_len[i] >= 1200 (server.py:91)                        QPP_ACC_SMALL
+ *   5. 1 <= DCID length <= QPP_CID_MAX and 6 + DCID length <= d_len[i],
+ *      checked here against d_len (a zero-length DCID cannot enter a
+ *      qpp_cidmap and stays the host's)                       QPP_ACC_CID
+ *   6. with QPP_A_NEED_TOKEN in accept_flags, token length > 0 (the server's
+ *      Retry mode, server.py:95-111: an Initial without a token is answered
+ *      with a Retry and needs no keys)                        QPP_ACC_NO_TOKEN
+ * Accepted (QPP_ACC_OK): d_ini[a] = {slot_client = d_acc_slot[2a], slot_server
+ * = d_acc_slot[2a + 1], cid_len, QPP_DERIVE_V2 for version 2, the DCID's bytes
+ * from the datagram at [6, 6 + DCID length), zero padded}; d_desc[i] = {in_off
+ * = out_off = d_off[i], len = the record's packet length, hdr_len = pn_off,
+ * flags = desc_flags, pn = 0, slot = d_acc_slot[2a], rsv = 0}; d_acc[a] =
+ * {desc = i, status, version = 0 for version 1 and 1 for version 2}.  Any
+ * other verdict: d_ini[a] names no slot (both QPP_SLOT_NONE) and no CID
+ * (cid_len 0, zero bytes), so qpp_keytab_derive_initial_device derives it and
+ * installs nothing; d_desc is not touched, so the inert descriptor qpp_route
+ * wrote stays; d_acc[a] = {QPP_DESC_NONE, status, 0}.  d_ini and d_acc are
+ * written whole for every candidate: the same input gives the same bytes.
+ * Only packet 0 of a datagram gets a descriptor here; the later packets of an
+ * accepted datagram keep QPP_DESC_NONE in their walk records.  A lane reads
+ * its own walk and route records, d_len[i] and the DCID's bytes: nothing at or
+ * past d_len[i].
+ * QPP_E_ARG: a NULL array with n_acc > 0, or an accept_flags bit other than
+ * QPP_A_NEED_TOKEN.  n_acc == 0 returns QPP_OK and launches nothing. */
+#define QPP_ACC_OK 0
+#define QPP_ACC_ROUTED 1
+#define QPP_ACC_NOT_INITIAL 2
+#define QPP_ACC_VERSION 3
+#define QPP_ACC_SMALL 4
+#define QPP_ACC_CID 5
+#define QPP_ACC_NO_TOKEN 6
+#define QPP_A_NEED_TOKEN 1u
+typedef struct qpp_accept_rec {
+    uint32_t desc;       /* the datagram's index (= its packet 0's descriptor), or QPP_DESC_NONE */
+    uint8_t status;      /* QPP_ACC_* */
+    uint8_t version;     /* accepted: 0 for QUIC version 1, 1 for version 2 */
+    uint8_t rsv[2];
+} qpp_accept_rec;        /* 8 bytes */
+int qpp_route_accept(const uint64_t *d_off, const uint32_t *d_len, uint32_t n, const uint8_t *d_in,
+                     const qpp_route_rec *d_route, const uint32_t *d_long_idx, uint32_t n_long,
+                     const qpp_walk_rec *d_walk, const uint32_t *d_walk_n, const uint32_t *d_acc_row,
+                     const uint32_t *d_acc_slot, uint32_t n_acc, uint32_t accept_flags, uint16_t desc_flags,
+                     qpp_initial *d_ini, qpp_desc *d_desc, qpp_accept_rec *d_acc, void *stream);
+/* qpp_route_accept launches of the accepting kernel (process-wide, since the
+ * library loaded).  Diagnostic: a batch without candidates makes none. */
+uint64_t qpp_route_accept_launches(void);
+
 /* Header-protection masks: replaces HeaderProtection_mask (_crypto.c:278-287).
  * d_samples: n x 16 bytes, d_masks: n x 16 bytes (first 5 used). */
 int qpp_hp_mask(const qpp_keytab *kt, const uint32_t *d_slots, const uint8_t *d_samples,
@@ -496,6 +592,39 @@ int qpp_session_route_walk_unprotect(qpp_session *s, const qpp_keytab *kt, const
                                      uint16_t desc_flags, uint8_t *out, size_t out_len, qpp_desc *desc_out,
                                      qpp_route_rec *route_out, qpp_result *res, qpp_walk_rec *walk_out,
                                      uint32_t *walk_n_out);
+/* qpp_session_route_walk_unprotect for a server that also takes on new
+ * connections: between the walk and the unprotect, qpp_route_accept picks
+ * the unrouted Initials among the candidates acc_row[n_acc] (rows of
+ * long_idx) and qpp_keytab_derive_initial_device derives and installs their
+ * keys in the slots acc_slot[2 n_acc], so the one unprotect launch decrypts
+ * their first packets too.  The sequence is one H2D, the routing kernel, the
+ * walking kernel, the accepting kernel, the derivation, the slot expansion,
+ * one unplanned unprotect over n + 3 n_long descriptors, one D2H.  The new
+ * arrays ride in the same scratch copy in each direction; the records, the key
+ * material and the secrets are device scratch of the session.  acc_out[n_acc]
+ * receives the qpp_accept_rec records, km_out[2 n_acc] and secrets_out[2 n_acc
+ * x 32] what qpp_keytab_derive_initial returns ([2a] the client direction of
+ * candidate a, [2a + 1] its server direction; a rejected candidate's carry
+ * QPP_SLOT_NONE and keys nobody uses).  kt is not const: every acc_slot is
+ * noted in its bookkeeping (qpp_keytab_derive_initial_device), and the caller
+ * clears those of the candidates the device rejected.
+ * Checked on the host before anything is launched or noted, besides what the
+ * walk form checks: acc_row strictly increasing and < n_long, every
+ * acc_slot[2a] < capacity, every acc_slot[2a + 1] < capacity or QPP_SLOT_NONE,
+ * all given slots pairwise distinct, n_acc <= 2^24, no accept_flags bit other
+ * than QPP_A_NEED_TOKEN, and acc_out / km_out / secrets_out given when n_acc >
+ * 0.  A violation is QPP_E_ARG and nothing is touched.  With n_acc == 0 the
+ * call makes the same launches and returns the same bytes as
+ * qpp_session_route_walk_unprotect. */
+int qpp_session_accept_unprotect(qpp_session *s, qpp_keytab *kt, const qpp_cidmap *m, uint32_t cid_len,
+                                 const uint64_t *off, const uint32_t *len, uint32_t n, const uint8_t *in,
+                                 size_t in_len, const uint32_t *long_idx, uint32_t n_long,
+                                 const uint32_t *conn_slot, const uint64_t *conn_expected, uint32_t n_conn,
+                                 uint16_t desc_flags, const uint32_t *acc_row, const uint32_t *acc_slot,
+                                 uint32_t n_acc, uint32_t accept_flags, uint8_t *out, size_t out_len,
+                                 qpp_desc *desc_out, qpp_route_rec *route_out, qpp_result *res,
+                                 qpp_walk_rec *walk_out, uint32_t *walk_n_out, qpp_accept_rec *acc_out,
+                                 qpp_key_material *km_out, uint8_t *secrets_out);
 /* The session's own pinned staging buffers, sized for at least `bytes` of
  * input and of output and n packets; valid until the next call on the
  * session.  A caller that assembles its input straight into *h_in and passes
