@@ -637,7 +637,10 @@ __device__ __forceinline__ void write_header_v(const Pkt &P, int sub, bool maske
 //     keystream (rounds 1-2 from the packet's counter cache), the register
 //     prefetch of the next step's input, two buffer stores (dropped out of
 //     range; a partial tail block is stored by its lane with byte stores), two
-//     H^4 multiplies.
+//     H^4 multiplies.  BPL = 2: a wave whose lanes are all past the first step
+//     and at least three steps from their packet's end runs that step as a
+//     straight-line body of whole ciphertext blocks (inner2), any other
+//     wave-step with the per-lane block cases (step2).
 //   * Nothing of a packet waits in LDS: unprotect writes its header before the
 //     loop (the mask is known), protect in its first step (gcm_fast_hp) or
 //     after the loop; E_K(J0) stays in the lengths lane's registers.
@@ -859,6 +862,38 @@ __device__ __forceinline__ u32x4 gcm_packet(const Pkt &P, const KeySlot *ks, con
                 step2(i, k == 1, raw0, raw1, first_c);
                 i += 8;
             };
+            // An interior step: countdown k >= kInteriorK, after the first
+            // step.  The sequence [pad | Z | CT | lengths] has 8 S positions,
+            // so CT block j sits at position q + j and q + n_c + 1 = 8 S.  The
+            // step with countdown k holds positions 8 (S - k) .. 8 (S - k) + 7,
+            // i.e. CT blocks 8 (S - k) - q .. n_c + 8 - 8 k: at k >= 2 the last
+            // of them is at most n_c - 8, a whole block, and past the first
+            // step (k <= S - 1) the first is at least 8 - q >= 0 (q <= 8).  So
+            // both blocks of every lane are whole ciphertext blocks, with no
+            // padding, Z, partial tail, lengths block, close or tag load; and
+            // at k >= 3 the same holds for the step being prefetched, whose
+            // inputs are then the two blocks 128 bytes on.  Admitting k = 2
+            // too would keep ct_load's clamps on the prefetch of every interior
+            // step (the step after may be the last): more VALU per item at
+            // 1200 bytes than the one general step it saves
+            // (profiles/r17_gcm_interior_census.txt).
+            constexpr int kInteriorK = 3;
+            auto inner2 = [&]() {
+                const u32x4 raw0 = nxt0, raw1 = nxt1;
+                const uint32_t lo = cin + 16u * (uint32_t)i;
+                nxt0 = __builtin_amdgcn_raw_buffer_load_b128(B.in, (int)(lo + 128u), 0, 0);
+                nxt1 = __builtin_amdgcn_raw_buffer_load_b128(B.in, (int)(lo + 192u), 0, 0);
+                const Te Tl = te_now();
+                u32x4 ks0, ks1;
+                aes_ctr2<NR>(cc, (uint32_t)(i + 2), (uint32_t)(i + 6), rk, Tl, ks0, ks1);
+                const u32x4 out0 = raw0 ^ ks0, out1 = raw1 ^ ks1;
+                const uint32_t so = cout + 16u * (uint32_t)i;
+                __builtin_amdgcn_raw_buffer_store_b128(out0, B.out, (int)so, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(out1, B.out, (int)(so + 64u), 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+                acc = mul_h4(mul_h4(acc ^ (ENC ? out0 : raw0)) ^ (ENC ? out1 : raw1));
+                i += 8;
+            };
             QPP_PROBE_AT(4);
             // the first step is peeled: it alone may carry Z and the HP sample
             one2(S, std::true_type{});
@@ -878,7 +913,11 @@ __device__ __forceinline__ u32x4 gcm_packet(const Pkt &P, const KeySlot *ks, con
                     else if (kr >= 2) __builtin_amdgcn_s_setprio(1);
                     else __builtin_amdgcn_s_setprio(0);
                 }
-                one2(k, std::false_type{});
+                // the straight-line body when every lane still in the loop is
+                // at an interior step (lanes whose packet has ended are
+                // inactive here and have no say): a scalar branch
+                if (__builtin_amdgcn_ballot_w64(k < kInteriorK) == 0) inner2();
+                else one2(k, std::false_type{});
             }
             if (!ENC) got_tag = nxt0;
         }
