@@ -193,6 +193,35 @@ class PacketEngine:
                 np.frombuffer(route, dtype=L.ROUTE), np.frombuffer(res, dtype=L.RESULT),
                 np.frombuffer(walk, dtype=L.WALK).reshape(-1, L.WALK_MAX), np.frombuffer(walk_n, dtype=np.uint32))
 
+    def route_phase(self, route, next_slots, n_next: int, desc, n: int, inbuf, phase, stream=None) -> None:
+        """qpp_route_phase on device buffers, after route() (and route_walk())
+        on the same stream and before unprotect(): descriptors [0, n) whose
+        short header carries the other key phase are pointed at their
+        connection's next-phase slot `next_slots[route.conn]` (uint32; with
+        `route` None, `next_slots[i]` per descriptor) and `phase` (uint8, n)
+        says which were."""
+        _crypto.route_phase(self.table, 0 if route is None else _ptr(route), _ptr(next_slots), int(n_next),
+                            _ptr(desc), int(n), _ptr(inbuf), _ptr(phase), self._stream(stream))
+
+    def route_phase_unprotect_host(self, cid_map, cid_len: int, offs, lens, data, long_idx, conn_slot,
+                                   conn_expected, conn_next, out_len: int, flags: int = 0):
+        """route_walk_unprotect_host with the peers' key updates resolved on
+        the device (qpp_session_route_phase_unprotect): `conn_next` names a
+        next-phase slot or SLOT_NONE per connection, or is None.  Returns
+        (out, desc, route, results, walk, walk_n, phase)."""
+        out, desc, route, res, walk, walk_n, phase = _crypto.route_phase_unprotect_host(
+            self.table, cid_map, int(cid_len), np.ascontiguousarray(offs, dtype=np.uint64).tobytes(),
+            np.ascontiguousarray(lens, dtype=np.uint32).tobytes(), bytes(data),
+            np.ascontiguousarray(long_idx, dtype=np.uint32).tobytes(),
+            np.ascontiguousarray(conn_slot, dtype=np.uint32).tobytes(),
+            np.ascontiguousarray(conn_expected, dtype=np.uint64).tobytes(),
+            None if conn_next is None else np.ascontiguousarray(conn_next, dtype=np.uint32).tobytes(),
+            int(flags), int(out_len))
+        return (np.frombuffer(out, dtype=np.uint8), np.frombuffer(desc, dtype=L.DESC),
+                np.frombuffer(route, dtype=L.ROUTE), np.frombuffer(res, dtype=L.RESULT),
+                np.frombuffer(walk, dtype=L.WALK).reshape(-1, L.WALK_MAX), np.frombuffer(walk_n, dtype=np.uint32),
+                np.frombuffer(phase, dtype=L.PHASE))
+
     # ----------------------------------------------- host-buffer forms ----
 
     def protect_host(self, desc: np.ndarray, data, out_len: int):

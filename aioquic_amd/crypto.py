@@ -165,11 +165,21 @@ class CryptoContext:
         self.hp: Optional[HeaderProtection] = None
         self.cipher_suite: Optional[CipherSuite] = None
         self.secret: Optional[bytes] = None
+        self._drop_next()
+
+    def _drop_next(self, keep: Optional[AEAD] = None) -> None:
+        """Forget the cached next-phase context (cached_next_phase); its AEAD
+        leaves the batch key tables unless it is `keep`, the one just adopted."""
+        nxt = getattr(self, "_next", None)
+        self._next: Optional["CryptoContext"] = None
+        if nxt is not None and nxt.aead is not None and nxt.aead is not keep:
+            _release(nxt.aead)
 
     def setup(self, *, cipher_suite: CipherSuite, secret: bytes, version: int) -> None:
         suite = _SUITES[cipher_suite]
         key, iv, hp_key = derive_key_iv_hp(cipher_suite=cipher_suite, secret=secret, version=version)
         self.cipher_suite, self.secret, self.version = cipher_suite, secret, version
+        self._drop_next()
         self.aead = AEAD(suite.aead_name, key, iv)
         self.hp = HeaderProtection(suite.hp_name, hp_key)
         self._setup_cb("tls")
@@ -228,6 +238,7 @@ def apply_key_phase(self: CryptoContext, crypto: CryptoContext, trigger: str) ->
     """Adopt `crypto`'s AEAD key, phase and secret (the HP key is kept)."""
     old = self.aead
     self.aead, self.key_phase, self.secret = crypto.aead, crypto.key_phase, crypto.secret
+    self._drop_next(keep=self.aead)
     if old is not None and old is not self.aead:
         _release(old)
     hook = self._setup_cb
@@ -244,6 +255,17 @@ def next_key_phase(self: CryptoContext) -> CryptoContext:
     """A fresh context on the next key phase of `self`."""
     nxt = CryptoContext(key_phase=1 - int(bool(self.key_phase)))
     nxt.setup(cipher_suite=self.cipher_suite, secret=_updated_secret(self), version=self.version)
+    return nxt
+
+
+def cached_next_phase(self: CryptoContext) -> CryptoContext:
+    """next_key_phase(self), built once per phase and kept on the context:
+    setup, teardown and apply_key_phase drop it.  receive_routed(...,
+    next_phase=True) installs its AEAD key beside the current one, under the
+    current header-protection key, and adopts it when the peer updates."""
+    nxt = self._next
+    if nxt is None:
+        nxt = self._next = next_key_phase(self)
     return nxt
 
 
@@ -282,6 +304,14 @@ class CryptoPair:
     def _update_key(self, trigger: str) -> None:
         for ctx in (self.recv, self.send):
             apply_key_phase(ctx, next_key_phase(ctx), trigger=trigger)
+        self._update_key_requested = False
+
+    def _update_key_cached(self, trigger: str) -> None:
+        """_update_key whose receive direction adopts the cached next-phase
+        context (the one a packet of the batch was just decrypted with), so
+        the key slot bound to its AEAD becomes the current one as it is."""
+        apply_key_phase(self.recv, cached_next_phase(self.recv), trigger=trigger)
+        apply_key_phase(self.send, next_key_phase(self.send), trigger=trigger)
         self._update_key_requested = False
 
     def setup_initial(self, cid: bytes, is_client: bool, version: int) -> None:

@@ -1232,6 +1232,100 @@ static PyObject *py_route_walk_launches(PyObject *m, PyObject *unused)
     return PyLong_FromUnsignedLongLong(qpp_route_walk_launches());
 }
 
+/* route_phase(table, route_ptr (0: one d_next entry per descriptor), next_ptr, n_next, desc_ptr, n, in_ptr,
+ *             phase_ptr, stream) */
+static PyObject *py_route_phase(PyObject *m, PyObject *args)
+{
+    PyObject *t;
+    unsigned long long rp, np_, dp, ip, pp, sp;
+    unsigned int n_next, n;
+    if (!PyArg_ParseTuple(args, "OKKIKIKKK", &t, &rp, &np_, &n_next, &dp, &n, &ip, &pp, &sp)) return NULL;
+    qpp_keytab *kt = as_table(t);
+    if (!kt) return NULL;
+    int rc = qpp_route_phase(kt, as_ptr(rp), as_ptr(np_), n_next, as_ptr(dp), n, as_ptr(ip), as_ptr(pp), as_ptr(sp));
+    if (rc == QPP_E_ARG) {
+        PyErr_SetString(PyExc_ValueError, "bad route_phase arguments (a null buffer)");
+        return NULL;
+    }
+    if (check_rc(rc) < 0) return NULL;
+    Py_RETURN_NONE;
+}
+
+static PyObject *py_route_phase_launches(PyObject *m, PyObject *unused)
+{
+    return PyLong_FromUnsignedLongLong(qpp_route_phase_launches());
+}
+
+/* route_phase_unprotect_host(table, map, cid_len, offs_u64, lens_u32, data, long_idx_u32, conn_slot_u32 (x KEYSETS),
+ *                            conn_expected_u64 (x SPACES), conn_next_u32 or None, flags, out_len)
+ *     -> (out, desc, route, results, walk, walk_n, phase) */
+static PyObject *py_route_phase_unprotect_host(PyObject *m, PyObject *args)
+{
+    PyObject *t, *mo;
+    const char *offs, *lens, *data, *lidx, *cslot, *cexp, *cnext = NULL;
+    Py_ssize_t l_offs, l_lens, l_data, l_lidx, l_cslot, l_cexp, l_cnext = 0, out_len;
+    unsigned int cid_len, flags;
+    if (!PyArg_ParseTuple(args, "OOIy#y#y#y#y#y#z#In", &t, &mo, &cid_len, &offs, &l_offs, &lens, &l_lens, &data,
+                          &l_data, &lidx, &l_lidx, &cslot, &l_cslot, &cexp, &l_cexp, &cnext, &l_cnext, &flags,
+                          &out_len))
+        return NULL;
+    qpp_keytab *kt = as_table(t);
+    qpp_cidmap *map = kt ? as_cidmap(mo) : NULL;
+    if (!map) return NULL;
+    const Py_ssize_t n = l_lens / 4, nl = l_lidx / 4, nc = l_cslot / (4 * QPP_KEYSETS);
+    if (l_lens % 4 || l_lidx % 4 || l_cslot != nc * 4 * QPP_KEYSETS || l_offs != n * 8 ||
+        l_cexp != nc * 8 * QPP_SPACES || (cnext && l_cnext != nc * 4) || out_len < 0 || flags > 0xffff ||
+        n > 0x7fffffff || nc > 0x7fffffff || nl > 0x7fffffff || n + 3 * nl > 0x7fffffff) {
+        PyErr_SetString(PyExc_ValueError, "bad array lengths, flags or output length");
+        return NULL;
+    }
+    const Py_ssize_t nd = n + 3 * nl;
+    PyObject *out = PyBytes_FromStringAndSize(NULL, out_len);
+    PyObject *desc = PyBytes_FromStringAndSize(NULL, nd * (Py_ssize_t)sizeof(qpp_desc));
+    PyObject *route = PyBytes_FromStringAndSize(NULL, n * (Py_ssize_t)sizeof(qpp_route_rec));
+    PyObject *res = PyBytes_FromStringAndSize(NULL, nd * (Py_ssize_t)sizeof(qpp_result));
+    PyObject *walk = PyBytes_FromStringAndSize(NULL, nl * QPP_WALK_MAX * (Py_ssize_t)sizeof(qpp_walk_rec));
+    PyObject *walk_n = PyBytes_FromStringAndSize(NULL, nl * 4);
+    PyObject *phase = PyBytes_FromStringAndSize(NULL, n);
+    PyObject *ret = NULL;
+    qpp_session *s = out && desc && route && res && walk && walk_n && phase ? session() : NULL;
+    if (s) {
+        char *o = PyBytes_AsString(out);
+        /* an empty batch, or a refused one, leaves `out` as zeros */
+        memset(o, 0, (size_t)out_len);
+        memset(PyBytes_AsString(walk), 0, (size_t)PyBytes_Size(walk));
+        memset(PyBytes_AsString(phase), 0, (size_t)n);
+        int rc;
+        Py_BEGIN_ALLOW_THREADS
+        rc = qpp_session_route_phase_unprotect(s, kt, map, cid_len, (const uint64_t *)offs, (const uint32_t *)lens,
+                                               (uint32_t)n, (const uint8_t *)data, (size_t)l_data,
+                                               (const uint32_t *)lidx, (uint32_t)nl, (const uint32_t *)cslot,
+                                               (const uint64_t *)cexp, (uint32_t)nc, (const uint32_t *)cnext,
+                                               (uint16_t)flags, (uint8_t *)o, (size_t)out_len,
+                                               (qpp_desc *)PyBytes_AsString(desc),
+                                               (qpp_route_rec *)PyBytes_AsString(route),
+                                               (qpp_result *)PyBytes_AsString(res),
+                                               (qpp_walk_rec *)PyBytes_AsString(walk),
+                                               (uint32_t *)PyBytes_AsString(walk_n),
+                                               (uint8_t *)PyBytes_AsString(phase));
+        Py_END_ALLOW_THREADS
+        if (rc == QPP_E_ARG)
+            PyErr_SetString(PyExc_ValueError, "bad route arguments (cid_len outside 1..20, a datagram outside the "
+                                              "input or the output buffer, long_idx not strictly increasing below "
+                                              "n, or a next-phase slot outside the table); nothing was launched");
+        else if (check_rc(rc) == 0)
+            ret = PyTuple_Pack(7, out, desc, route, res, walk, walk_n, phase);
+    }
+    Py_XDECREF(out);
+    Py_XDECREF(desc);
+    Py_XDECREF(route);
+    Py_XDECREF(res);
+    Py_XDECREF(walk);
+    Py_XDECREF(walk_n);
+    Py_XDECREF(phase);
+    return ret;
+}
+
 /* route_accept(off_ptr, len_ptr, n, in_ptr, route_ptr, long_ptr, n_long, walk_ptr, walk_n_ptr, row_ptr, slot_ptr,
  *              n_acc, accept_flags, desc_flags, ini_ptr, desc_ptr, acc_ptr, stream) */
 static PyObject *py_route_accept(PyObject *m, PyObject *args)
@@ -2055,6 +2149,10 @@ typedef struct {
     uint8_t **od;
     const uint8_t **os_;
     size_t *ol, on, otot;
+    /* receive_routed_phase (both NULL otherwise): qpp_route_phase's verdict per descriptor, and per pair
+       whether a packet of the batch has rolled its keys (updated) */
+    const uint8_t *phase;
+    uint8_t *rolled;
 } ShortWalk;
 
 static int short_walk(ShortWalk *w)
@@ -2092,6 +2190,9 @@ static int short_walk(ShortWalk *w)
             if (!defer && launched) {
                 const uint64_t now = sx[sp];
                 defer = blocked_pair[p] || blocked_space[sp] || (!closed[c] && ri->status == QPP_S_KEY_PHASE);
+                /* the pair has rolled and this packet ran on the slot of the phase before: the general
+                   path's, as a flip is (it tries the phase after next and fails, crypto.py:91-96) */
+                if (!defer && !closed[c] && w->rolled && w->rolled[p] && !w->phase[x]) defer = 1;
                 if (!defer && !closed[c] && now != dk->pn && (ri->status == QPP_S_OK || ri->status == QPP_S_DECRYPT)) {
                     const int pn_len = (int)ri->hdr_len - (int)dk->hdr_len;
                     if (pn_len < 1 || pn_len > 4 || decode_pn_signed(ri->pn, pn_len, now) != (int64_t)ri->pn)
@@ -2120,6 +2221,9 @@ static int short_walk(ShortWalk *w)
                 rec = make_record(tp, alloc, f, 9);
             } else {
                 const uint64_t now = sx[sp];
+                /* a packet of the next phase that authenticates updates the keys inside decrypt_packet
+                   (crypto.py:184-192), before the reserved bits are looked at (connection.py:949-960) */
+                if (w->rolled && w->phase[x] && ri->status == QPP_S_OK) w->rolled[p] = 1;
                 if (ri->status == QPP_S_OK && (hout[dk->out_off] & 0x18)) {
                     /* connection.py:949-960: the close, before :984-985 */
                     closed[c] = 1;
@@ -2384,18 +2488,39 @@ done:
  * in-order walk is always the caller's: the third item carries what the
  * device found whenever a long-header datagram was listed.  The fourth item
  * holds the packed qpp_accept_rec, 2 x qpp_key_material and 2 x 32 secret
- * bytes of every candidate. */
-static PyObject *receive_routed_impl(PyObject *args, int accept)
+ * bytes of every candidate.
+ *
+ * receive_routed_phase(the arguments of receive_routed, pair_next_u32)
+ *     -> (route, None | (records, deferred, space_exp after, conn_closed after, pair_rolled_u8), None | (...))
+ * receive_routed with the peers' key updates resolved on the device: the call
+ * is qpp_session_route_phase_unprotect, and pair_next names, per entry of
+ * pair_slot, the slot of that pair's next key phase (the current HP key, the
+ * next AEAD key, the other phase bit) or 0xffffffff.  A connection closed on
+ * entry gets none.  The in-order walk then follows CryptoPair.decrypt_packet
+ * (quic/crypto.py:184-192): a packet the device pointed at the next slot that
+ * authenticates rolls its pair, before its reserved bits are looked at; one
+ * that fails its tag is a payload_decrypt_error and rolls nothing; once a pair
+ * has rolled, a packet that ran on the slot of the phase before is deferred,
+ * as a QPP_S_KEY_PHASE packet is.  pair_rolled has one byte per pair_slot
+ * entry: the pairs whose keys the caller must now update.  The walk's arrays
+ * may be empty when no datagram starts with a long header. */
+static PyObject *receive_routed_impl(PyObject *args, int mode)
 {
+    const int accept = mode == 1, phased = mode == 2;
     PyObject *t, *mo, *dgs, *rec_type, *ptype, *epoch;
     const char *a_pair, *a_space, *a_pslot, *a_sexp, *a_closed, *a_kslot, *a_kexp, *a_arow = NULL, *a_aslot = NULL;
-    Py_ssize_t l_pair, l_space, l_pslot, l_sexp, l_closed, l_kslot, l_kexp, l_arow = 0, l_aslot = 0;
+    const char *a_pnext = NULL;
+    Py_ssize_t l_pair, l_space, l_pslot, l_sexp, l_closed, l_kslot, l_kexp, l_arow = 0, l_aslot = 0, l_pnext = 0;
     unsigned int cid_len, accept_flags = 0;
     int walk;
     if (!(accept ? PyArg_ParseTuple(args, "OOIO!y#y#y#y#y#y#OOOy#iy#y#I", &t, &mo, &cid_len, &PyList_Type, &dgs, &a_pair,
                                     &l_pair, &a_space, &l_space, &a_pslot, &l_pslot, &a_sexp, &l_sexp, &a_kslot,
                                     &l_kslot, &a_kexp, &l_kexp, &rec_type, &ptype, &epoch, &a_closed, &l_closed, &walk,
                                     &a_arow, &l_arow, &a_aslot, &l_aslot, &accept_flags)
+          : phased ? PyArg_ParseTuple(args, "OOIO!y#y#y#y#y#y#OOOy#iy#", &t, &mo, &cid_len, &PyList_Type, &dgs, &a_pair,
+                                      &l_pair, &a_space, &l_space, &a_pslot, &l_pslot, &a_sexp, &l_sexp, &a_kslot,
+                                      &l_kslot, &a_kexp, &l_kexp, &rec_type, &ptype, &epoch, &a_closed, &l_closed,
+                                      &walk, &a_pnext, &l_pnext)
                  : PyArg_ParseTuple(args, "OOIO!y#y#y#y#y#y#OOOy#i", &t, &mo, &cid_len, &PyList_Type, &dgs, &a_pair,
                                     &l_pair, &a_space, &l_space, &a_pslot, &l_pslot, &a_sexp, &l_sexp, &a_kslot,
                                     &l_kslot, &a_kexp, &l_kexp, &rec_type, &ptype, &epoch, &a_closed, &l_closed,
@@ -2431,6 +2556,10 @@ static PyObject *receive_routed_impl(PyObject *args, int accept)
         PyErr_SetString(PyExc_ValueError, "batch too large");
         return NULL;
     }
+    if (phased && l_pnext != l_pslot) {
+        PyErr_SetString(PyExc_ValueError, "pair_next: one u32 per pair_slot entry");
+        return NULL;
+    }
     const Py_ssize_t na = l_arow / 4;
     if (accept && (l_arow % 4 || l_aslot != 8 * na || na > n || !walk || !(l_kslot || l_kexp || nc == 0))) {
         PyErr_SetString(PyExc_ValueError, "acc_row: whole u32 items, no more than datagrams; acc_slot: two u32 each; "
@@ -2464,7 +2593,22 @@ static PyObject *receive_routed_impl(PyObject *args, int accept)
     size_t *ol = (size_t *)malloc((2 * (size_t)n + 1) * sizeof(size_t));
     PyObject *ret = NULL, *route = NULL, *recs = NULL, *deferred = NULL, *sexp_out = NULL, *closed_out = NULL;
     PyObject *empty = NULL, *minus1 = NULL, *zero = NULL, *s_key = NULL, *s_dec = NULL, *s_rsv = NULL, *s_closed = NULL;
-    PyObject *walked = NULL, *longs = NULL, *acc = NULL, *km = NULL, *secrets = NULL;
+    PyObject *walked = NULL, *longs = NULL, *acc = NULL, *km = NULL, *secrets = NULL, *rolled_out = NULL;
+    /* phased: the per-connection next-phase slots, the device's verdicts, and the walk form's arrays when
+       the caller gave none (a batch with no long header) */
+    uint32_t *cnext = NULL, *ks_own = NULL;
+    uint64_t *ke_own = NULL;
+    uint8_t *phase = NULL;
+    if (phased) {
+        cnext = (uint32_t *)malloc(nc1 * sizeof(uint32_t));
+        phase = (uint8_t *)calloc(n1, 1);
+        if (!cnext || !phase) goto nomem;
+        if (!(l_kslot || l_kexp)) {
+            ks_own = (uint32_t *)malloc(nc1 * QPP_KEYSETS * sizeof(uint32_t));
+            ke_own = (uint64_t *)calloc(nc1 * QPP_SPACES, sizeof(uint64_t));
+            if (!ks_own || !ke_own) goto nomem;
+        }
+    }
     if (accept) {
         acc = PyBytes_FromStringAndSize(NULL, na * (Py_ssize_t)sizeof(qpp_accept_rec));
         km = PyBytes_FromStringAndSize(NULL, na * 2 * (Py_ssize_t)sizeof(qpp_key_material));
@@ -2508,6 +2652,14 @@ static PyObject *receive_routed_impl(PyObject *args, int accept)
     for (Py_ssize_t c = 0; c < nc; ++c) {
         cslot[c] = ((const uint8_t *)a_closed)[c] ? QPP_SLOT_NONE : pslot[cpair[c]];
         cexp[c] = ((const uint64_t *)a_sexp)[cspace[c]];
+        if (phased) {
+            cnext[c] = ((const uint8_t *)a_closed)[c] ? QPP_SLOT_NONE : ((const uint32_t *)a_pnext)[cpair[c]];
+            if (ks_own) {
+                for (int j = 0; j < QPP_KEYSETS - 1; ++j) ks_own[c * QPP_KEYSETS + j] = QPP_SLOT_NONE;
+                ks_own[c * QPP_KEYSETS + QPP_KEYSETS - 1] = cslot[c];
+                ke_own[c * QPP_SPACES + QPP_SPACES - 1] = cexp[c];
+            }
+        }
     }
     route = PyBytes_FromStringAndSize(NULL, n * (Py_ssize_t)sizeof(qpp_route_rec));
     if (!route) goto done;
@@ -2528,6 +2680,11 @@ static PyObject *receive_routed_impl(PyObject *args, int accept)
                                               (qpp_accept_rec *)PyBytes_AsString(acc),
                                               (qpp_key_material *)PyBytes_AsString(km),
                                               (uint8_t *)PyBytes_AsString(secrets));
+        else if (phased)
+            rc = qpp_session_route_phase_unprotect(ss, kt, map, cid_len, offs, lens, (uint32_t)n, hin, total, lidx, nl,
+                                                   ks_own ? ks_own : (const uint32_t *)a_kslot,
+                                                   ke_own ? ke_own : (const uint64_t *)a_kexp, (uint32_t)nc, cnext,
+                                                   0, hout, total, desc, (qpp_route_rec *)rr, res, wrec, wn, phase);
         else if (nl)
             rc = qpp_session_route_walk_unprotect(ss, kt, map, cid_len, offs, lens, (uint32_t)n, hin, total, lidx, nl,
                                                   (const uint32_t *)a_kslot, (const uint64_t *)a_kexp, (uint32_t)nc,
@@ -2536,6 +2693,11 @@ static PyObject *receive_routed_impl(PyObject *args, int accept)
             rc = qpp_session_route_unprotect(ss, kt, map, cid_len, offs, lens, (uint32_t)n, hin, total, cslot, cexp,
                                              (uint32_t)nc, 0, hout, total, desc, (qpp_route_rec *)rr, res);
         Py_END_ALLOW_THREADS
+        if (phased && rc == QPP_E_ARG) {
+            PyErr_SetString(PyExc_ValueError, "bad arguments (a next-phase slot outside the table); nothing was "
+                                              "launched");
+            goto done;
+        }
         if (accept && rc == QPP_E_ARG) {
             PyErr_SetString(PyExc_ValueError, "bad accept arguments (acc_row not strictly increasing below the listed "
                                               "datagrams, a slot outside the table or named twice, or an unknown "
@@ -2592,6 +2754,11 @@ static PyObject *receive_routed_impl(PyObject *args, int accept)
     s_dec = PyUnicode_FromString("payload_decrypt_error");
     s_rsv = PyUnicode_FromString("reserved_bits");
     s_closed = PyUnicode_FromString("connection_closed");
+    if (phased) {
+        rolled_out = PyBytes_FromStringAndSize(NULL, n_pairs);
+        if (!rolled_out) goto nomem;
+        memset(PyBytes_AsString(rolled_out), 0, (size_t)n_pairs);
+    }
     if (!sexp_out || !closed_out || !recs || !deferred || !empty || !minus1 || !zero || !s_key || !s_dec || !s_rsv ||
         !s_closed)
         goto nomem;
@@ -2599,20 +2766,26 @@ static PyObject *receive_routed_impl(PyObject *args, int accept)
         ShortWalk w = {nr, dg, dg, conn_of, slot_of, cpair, cspace, desc, res,
                        hout, (uint64_t *)PyBytes_AsString(sexp_out), (uint8_t *)PyBytes_AsString(closed_out),
                        blocked_pair, blocked_space, blocked_conn, recs, deferred, tp, alloc, ptype, epoch, empty,
-                       minus1, zero, s_key, s_dec, s_rsv, s_closed, od, os_, ol, 0, 0};
+                       minus1, zero, s_key, s_dec, s_rsv, s_closed, od, os_, ol, 0, 0, NULL, NULL};
+        if (phased) {
+            w.phase = phase;
+            w.rolled = (uint8_t *)PyBytes_AsString(rolled_out);
+        }
         if (short_walk(&w) < 0) goto done;
         Py_BEGIN_ALLOW_THREADS
         par_copy(od, os_, ol, w.on, w.otot);
         Py_END_ALLOW_THREADS
     }
-    walked = PyTuple_Pack(4, recs, deferred, sexp_out, closed_out);
+    walked = phased ? PyTuple_Pack(5, recs, deferred, sexp_out, closed_out, rolled_out)
+                    : PyTuple_Pack(4, recs, deferred, sexp_out, closed_out);
     if (walked) ret = PyTuple_Pack(3, route, walked, Py_None);
     goto done;
 nomem:
     PyErr_NoMemory();
 done:
     free(offs), free(cexp), free(lens), free(cslot), free(conn_of), free(slot_of), free(dg), free(desc), free(res);
-    free(lidx), free(wrec), free(wn);
+    free(lidx), free(wrec), free(wn), free(cnext), free(phase), free(ks_own), free(ke_own);
+    Py_XDECREF(rolled_out);
     Py_XDECREF(longs);
     Py_XDECREF(acc);
     Py_XDECREF(km);
@@ -2638,6 +2811,7 @@ done:
 
 static PyObject *py_receive_routed(PyObject *m, PyObject *args) { return receive_routed_impl(args, 0); }
 static PyObject *py_receive_accept(PyObject *m, PyObject *args) { return receive_routed_impl(args, 1); }
+static PyObject *py_receive_routed_phase(PyObject *m, PyObject *args) { return receive_routed_impl(args, 2); }
 
 /* long_dcids(datagrams) -> None when no bytes object of the list starts with
  * a long header (first byte, bit 7), else the set of the destination CIDs of
@@ -2745,6 +2919,12 @@ static PyMethodDef module_methods[] = {
      "qpp_session_route_walk_unprotect on host buffers"},
     {"route_walk_launches", py_route_walk_launches, METH_NOARGS, "qpp_route_walk_launches()"},
     {"route_accept", py_route_accept, METH_VARARGS, "qpp_route_accept on device buffers"},
+    {"route_phase", py_route_phase, METH_VARARGS, "qpp_route_phase on device buffers"},
+    {"route_phase_launches", py_route_phase_launches, METH_NOARGS, "qpp_route_phase_launches()"},
+    {"route_phase_unprotect_host", py_route_phase_unprotect_host, METH_VARARGS,
+     "qpp_session_route_phase_unprotect: route, walk, resolve key phases and unprotect host buffers in one call"},
+    {"receive_routed_phase", py_receive_routed_phase, METH_VARARGS,
+     "receive_routed with a next-phase key slot per pair: peers' key updates resolved on the device"},
     {"route_accept_launches", py_route_accept_launches, METH_NOARGS, "qpp_route_accept_launches()"},
     {"receive_accept", py_receive_accept, METH_VARARGS,
      "receive_routed with the unrouted Initials among the candidates accepted on the device "

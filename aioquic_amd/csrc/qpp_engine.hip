@@ -28,6 +28,7 @@
 #include "qpp_device.h"
 #include "qpp_hkdf.h"
 #include "qpp_internal.h"
+#include "qpp_phase.h"
 
 namespace qpp {
 
@@ -2473,6 +2474,61 @@ __global__ __launch_bounds__(kMaskWG) void k_hp_mask(const KeySlot *__restrict__
     st16(masks + 16 * (size_t)i, m);
 }
 
+// Key-phase resolution ahead of the unprotect (qpp_route_phase, qpp_phase.h):
+// one lane per descriptor, the launch shape of k_hp_mask.  The current slot's
+// header-protection key unmasks the first byte of a packet of either phase; a
+// short header whose key-phase bit is not the current slot's is pointed at its
+// connection's next-phase slot, so the packet kernels meet a descriptor whose
+// slot matches the packet.  A lane writes d_phase[i] always and d_desc[i].slot
+// only when it re-points: plain vector stores, no atomics.  It reads byte 0
+// and the sixteen sample bytes of its packet, and those only once
+// qpp_ph::eligible has placed them inside the packet.
+__global__ __launch_bounds__(kMaskWG) void k_phase(const KeySlot *__restrict__ slots, uint32_t cap,
+                                                   const qpp_route_rec *__restrict__ route,
+                                                   const uint32_t *__restrict__ next, uint32_t n_next,
+                                                   qpp_desc *__restrict__ desc, uint32_t n,
+                                                   const uint8_t *__restrict__ gin,
+                                                   uint8_t *__restrict__ phase)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t te[kTeBytes];
+    const uint32_t i = blockIdx.x * kMaskWG + threadIdx.x;
+    // everything the decision reads is requested before the AES image is built
+    bool act = false;
+    uint32_t s0i = kNoSlot, s1i = kNoSlot, b0 = 0;
+    qpp_ph::Slot s0 = {qpp_ph::kSuiteEmpty, 0}, s1 = {qpp_ph::kSuiteEmpty, 0};
+    u32x4 smp = {0, 0, 0, 0};
+    if (i < n) {
+        const qpp_desc d = desc[i];
+        uint32_t e = i;
+        if (route) {
+            const qpp_route_rec r = route[i];
+            e = qpp_ph::next_entry(true, r.cls, r.conn, n_next, i);
+        }
+        if (e != qpp_ph::kNoEntry) s1i = next[e];
+        s0i = d.slot;
+        if (s0i < cap) s0 = qpp_ph::Slot{slots[s0i].suite, slots[s0i].key_phase};
+        if (s1i < cap) s1 = qpp_ph::Slot{slots[s1i].suite, slots[s1i].key_phase};
+        const qpp_ph::Desc pd = {d.in_off, d.out_off, d.len, d.hdr_len, d.flags, d.pn, d.slot, d.rsv};
+        act = qpp_ph::eligible(pd, s0, s1);
+        if (act) {
+            const uint8_t *src = gin + d.in_off;
+            b0 = src[0];
+            smp = ld16(src + qpp_ph::sample_off(pd));
+        }
+    }
+    load_te<kMaskWG>(te);
+    __syncthreads();
+    const LdsTe T{te, (uint32_t)(threadIdx.x & 31) * 4};
+    if (i >= n) return;
+    uint8_t flip = 0;
+    if (act) {
+        const u32x4 m = hp_mask_any(slots + s0i, s0.suite, smp, T);
+        flip = qpp_ph::flips((uint8_t)b0, (uint8_t)byte_of(m, 0), s0.key_phase) ? 1 : 0;
+    }
+    if (flip) desc[i].slot = s1i;
+    phase[i] = flip;
+}
+
 // --------------------------------------------------------------- key setup --
 
 // FIPS-197 sec. 5.2 in little-endian words (RotWord = rotr 8, Rcon in byte 0).
@@ -3425,6 +3481,23 @@ int qpp_hp_mask(const qpp_keytab *kt, const uint32_t *d_slots, const uint8_t *d_
     HIPCHK(hipGetLastError());
     return QPP_OK;
 }
+
+static std::atomic<uint64_t> g_phase_launches{0};
+
+int qpp_route_phase(const qpp_keytab *kt, const qpp_route_rec *d_route, const uint32_t *d_next, uint32_t n_next,
+                    qpp_desc *d_desc, uint32_t n, const uint8_t *d_in, uint8_t *d_phase, void *stream)
+{
+    if (!kt) return QPP_E_ARG;
+    if (n == 0) return QPP_OK;
+    if (!d_next || !d_desc || !d_in || !d_phase) return QPP_E_ARG;
+    hipLaunchKernelGGL(k_phase, dim3((n + kMaskWG - 1) / kMaskWG), dim3(kMaskWG), 0, (hipStream_t)stream,
+                       kt->d_slots, kt->cap, d_route, d_next, n_next, d_desc, n, d_in, d_phase);
+    HIPCHK(hipGetLastError());
+    g_phase_launches.fetch_add(1, std::memory_order_relaxed);
+    return QPP_OK;
+}
+
+uint64_t qpp_route_phase_launches(void) { return g_phase_launches.load(std::memory_order_relaxed); }
 
 int qpp_internal_launch_xfer(uint8_t *d0, const uint8_t *s0, size_t n0, uint8_t *d1, const uint8_t *s1, size_t n1,
                              hipStream_t st)

@@ -520,7 +520,8 @@ static int route_unprotect(qpp_session *s, const qpp_keytab *kt, const qpp_cidma
                            bool walk_form, const uint32_t *long_idx, uint32_t n_long, const uint32_t *conn_slot,
                            const uint64_t *conn_expected, uint32_t n_conn, uint16_t desc_flags, uint8_t *out,
                            size_t out_len, qpp_desc *desc_out, qpp_route_rec *route_out, qpp_result *res,
-                           qpp_walk_rec *walk_out, uint32_t *walk_n_out, const AcceptArgs *ac = NULL)
+                           qpp_walk_rec *walk_out, uint32_t *walk_n_out, const AcceptArgs *ac = NULL,
+                           const uint32_t *conn_next = NULL, uint8_t *phase_out = NULL)
 {
     if (!s || !kt || !m || cid_len < 1 || cid_len > QPP_CID_MAX) return QPP_E_ARG;
     const uint32_t n_acc = ac ? ac->n : 0;
@@ -537,6 +538,16 @@ static int route_unprotect(qpp_session *s, const qpp_keytab *kt, const qpp_cidma
             return QPP_E_ARG;
     for (uint32_t r = 0; r < n_long; ++r)
         if (long_idx[r] >= n || (r && long_idx[r] <= long_idx[r - 1])) return QPP_E_ARG;
+    // next-phase slots: inside the table or none; the resolving kernel runs only when one is named
+    bool any_next = false;
+    if (conn_next) {
+        if (!phase_out) return QPP_E_ARG;
+        const uint32_t cap = qpp_keytab_capacity(kt);
+        for (uint32_t c = 0; c < n_conn; ++c) {
+            if (conn_next[c] >= cap && conn_next[c] != QPP_SLOT_NONE) return QPP_E_ARG;
+            any_next = any_next || conn_next[c] != QPP_SLOT_NONE;
+        }
+    }
     if (n_acc) {
         if (!ac->row || !ac->slot || !ac->acc_out || !ac->km_out || !ac->secrets_out || n_acc > (1u << 24))
             return QPP_E_ARG;
@@ -567,7 +578,8 @@ static int route_unprotect(qpp_session *s, const qpp_keytab *kt, const qpp_cidma
                  o_kexp = o_kslot + (n_long ? al256((size_t)n_conn * QPP_KEYSETS * 4) : 0),
                  o_arow = o_kexp + (n_long ? al256((size_t)n_conn * QPP_SPACES * 8) : 0),
                  o_aslot = o_arow + (n_acc ? al256((size_t)n_acc * 4) : 0),
-                 up = o_aslot + (n_acc ? al256((size_t)n_acc * 8) : 0);
+                 o_next = o_aslot + (n_acc ? al256((size_t)n_acc * 8) : 0),
+                 up = o_next + (any_next ? al256((size_t)n_conn * 4) : 0);
     const size_t o_route = al256((size_t)nd * sizeof(qpp_desc)),
                  o_res = o_route + al256((size_t)n * sizeof(qpp_route_rec)),
                  o_walk = o_res + al256((size_t)nd * sizeof(qpp_result)),
@@ -575,7 +587,8 @@ static int route_unprotect(qpp_session *s, const qpp_keytab *kt, const qpp_cidma
                  o_acc = o_walkn + (n_long ? al256((size_t)n_long * 4) : 0),
                  o_km = o_acc + (n_acc ? al256((size_t)n_acc * sizeof(qpp_accept_rec)) : 0),
                  o_sec = o_km + (n_acc ? al256((size_t)n_acc * 2 * sizeof(qpp_key_material)) : 0),
-                 down = o_sec + (n_acc ? al256((size_t)n_acc * 64) : 0);
+                 o_phase = o_sec + (n_acc ? al256((size_t)n_acc * 64) : 0),
+                 down = o_phase + (any_next ? al256((size_t)n) : 0);
     // the candidates' qpp_initial records never leave the device: scratch past both copies
     const size_t ini_bytes = n_acc ? al256((size_t)n_acc * sizeof(qpp_initial)) : 0;
     qpp_session_bufs b;
@@ -607,6 +620,7 @@ static int route_unprotect(qpp_session *s, const qpp_keytab *kt, const qpp_cidma
         memcpy(hu + o_arow, ac->row, (size_t)n_acc * 4);
         memcpy(hu + o_aslot, ac->slot, (size_t)n_acc * 8);
     }
+    if (any_next) memcpy(hu + o_next, conn_next, (size_t)n_conn * 4);
     if (in_len && in != b.h_in) memcpy(b.h_in, in, in_len);  // staged by the caller already?
     HIPCHK(hipMemcpyAsync(du, hu, up, hipMemcpyHostToDevice, b.stream));
     if (in_len) HIPCHK(hipMemcpyAsync(b.d_in, b.h_in, in_len, hipMemcpyHostToDevice, b.stream));
@@ -640,6 +654,12 @@ static int route_unprotect(qpp_session *s, const qpp_keytab *kt, const qpp_cidma
                                               dd + o_sec, b.stream);
         if (rc != QPP_OK) return rc;
     }
+    if (any_next) {
+        // the walk's extra descriptors [n, nd) keep the slot they have
+        rc = qpp_route_phase(kt, d_route, (const uint32_t *)(du + o_next), n_conn, d_desc, n, b.d_in, dd + o_phase,
+                             b.stream);
+        if (rc != QPP_OK) return rc;
+    }
     rc = qpp_unprotect(kt, d_desc, nd, b.d_in, b.d_out, d_res, b.stream);
     if (rc != QPP_OK) return rc;
     if (out_len) HIPCHK(hipMemcpyAsync(b.h_out, b.d_out, out_len, hipMemcpyDeviceToHost, b.stream));
@@ -653,6 +673,8 @@ static int route_unprotect(qpp_session *s, const qpp_keytab *kt, const qpp_cidma
         memcpy(walk_out, hd + o_walk, (size_t)n_long * QPP_WALK_MAX * sizeof(qpp_walk_rec));
         memcpy(walk_n_out, hd + o_walkn, (size_t)n_long * 4);
     }
+    if (any_next) memcpy(phase_out, hd + o_phase, (size_t)n);
+    else if (phase_out) memset(phase_out, 0, (size_t)n);
     if (n_acc) {
         memcpy(ac->acc_out, hd + o_acc, (size_t)n_acc * sizeof(qpp_accept_rec));
         memcpy(ac->km_out, hd + o_km, (size_t)n_acc * 2 * sizeof(qpp_key_material));
@@ -693,6 +715,19 @@ int qpp_session_route_walk_unprotect(qpp_session *s, const qpp_keytab *kt, const
     return settle(s, route_unprotect(s, kt, m, cid_len, off, len, n, in, in_len, true, long_idx, n_long, conn_slot,
                                      conn_expected, n_conn, desc_flags, out, out_len, desc_out, route_out, res,
                                      walk_out, walk_n_out));
+}
+
+int qpp_session_route_phase_unprotect(qpp_session *s, const qpp_keytab *kt, const qpp_cidmap *m, uint32_t cid_len,
+                                      const uint64_t *off, const uint32_t *len, uint32_t n, const uint8_t *in,
+                                      size_t in_len, const uint32_t *long_idx, uint32_t n_long,
+                                      const uint32_t *conn_slot, const uint64_t *conn_expected, uint32_t n_conn,
+                                      const uint32_t *conn_next, uint16_t desc_flags, uint8_t *out, size_t out_len,
+                                      qpp_desc *desc_out, qpp_route_rec *route_out, qpp_result *res,
+                                      qpp_walk_rec *walk_out, uint32_t *walk_n_out, uint8_t *phase_out)
+{
+    return settle(s, route_unprotect(s, kt, m, cid_len, off, len, n, in, in_len, true, long_idx, n_long, conn_slot,
+                                     conn_expected, n_conn, desc_flags, out, out_len, desc_out, route_out, res,
+                                     walk_out, walk_n_out, NULL, conn_next, phase_out));
 }
 
 int qpp_session_accept_unprotect(qpp_session *s, qpp_keytab *kt, const qpp_cidmap *m, uint32_t cid_len,

@@ -98,6 +98,12 @@ W_OK, W_PARSE, W_HOST = 0, 1, 2
 ACCEPT = np.dtype([("desc", "<u4"), ("status", "u1"), ("version", "u1"), ("rsv", "u1", (2,))])
 ACC_OK, ACC_ROUTED, ACC_NOT_INITIAL, ACC_VERSION, ACC_SMALL, ACC_CID, ACC_NO_TOKEN = 0, 1, 2, 3, 4, 5, 6
 A_NEED_TOKEN = 1  # QPP_A_NEED_TOKEN: the server's Retry mode, an Initial must carry a token
+# qpp_route_phase: one verdict byte per descriptor (PHASE_NEXT: the descriptor
+# was pointed at its connection's next-phase slot), and the per-connection
+# next-phase slots it consults (a slot, or SLOT_NONE)
+PHASE = np.dtype("u1")
+PHASE_CURRENT, PHASE_NEXT = 0, 1
+NEXT_SLOT = np.dtype("<u4")
 assert DESC.itemsize == 40 and RESULT.itemsize == 16 and KEY_MATERIAL.itemsize == 84
 assert WALK.itemsize == 24 and ACCEPT.itemsize == 8
 assert SECRET.itemsize == 80 and INITIAL.itemsize == 32

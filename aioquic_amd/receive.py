@@ -45,7 +45,7 @@ from ._crypto import CryptoError
 from .batch_io import (ConnectionClosedError, ReceiveBatch, ReservedBitsError, _initial_directions, _install_initial,
                        default_slots, setup_initial_batch)
 from .buffer import Buffer
-from .crypto import KeyUnavailableError
+from .crypto import KeyUnavailableError, cached_next_phase
 from .packet import (
     PACKET_FIXED_BIT,
     PACKET_LONG_HEADER,
@@ -503,7 +503,8 @@ def _routed_long(conns, datagrams, cid_len: int, idx: list, cls, rconn, longs, s
     return _finish(items, out, queued, results)
 
 
-def receive_routed(router, datagrams: Sequence[bytes]) -> Tuple[List[ReceivedPacket], List[Tuple[int, int]]]:
+def receive_routed(router, datagrams: Sequence[bytes], *,
+                   next_phase: bool = False) -> Tuple[List[ReceivedPacket], List[Tuple[int, int]]]:
     """receive_datagrams for raw datagrams nobody has demultiplexed: the
     device routes each to its connection by connection ID (route.CidRouter,
     qpp_route), instead of the reference's per-datagram pull_quic_header and
@@ -533,26 +534,63 @@ def receive_routed(router, datagrams: Sequence[bytes]) -> Tuple[List[ReceivedPac
     the device leaves to the host walk (more than layout.WALK_MAX packets, a
     header past layout.MAX_HDR), a keyed Initial of a supported version that
     is neither 1 nor 2, and a key table too small for the reached
-    connections' key-sets beside the 1-RTT ones."""
+    connections' key-sets beside the 1-RTT ones.
+
+    A peer's key update (a short header whose key-phase bit flipped,
+    crypto.py:91-96) is deferred to ReceiveBatch by default: the packet and
+    every later one of its connection in the batch are uploaded and launched
+    again.  With `next_phase`, every keyed 1-RTT receive context also gets a
+    slot for its next key phase (crypto.cached_next_phase: the next AEAD key
+    under the current header-protection key, which a key update keeps), in the
+    same assign() as the batch's other keys, and a kernel ahead of the
+    unprotect points each flipped packet's descriptor at it (qpp_route_phase),
+    so the one launch decrypts both phases.  The in-order walk then rolls a
+    pair at its first next-phase packet that authenticates, as
+    CryptoPair.decrypt_packet does (crypto.py:184-192); the rolled pairs adopt
+    their cached contexts before anything deferred runs (an old-phase packet
+    after the update still is: the reference tries it on the phase after next
+    and fails).  A batch on the general path, one whose long headers reach
+    known connections (_routed_long), and a key table too small for the next
+    slots beside the batch's other keys run without next slots, as by default."""
     datagrams = datagrams if isinstance(datagrams, list) else list(datagrams)
     if not datagrams:
         return [], []
     conns = router.conns
     general = any(c is not None and c.is_client and c.host_cids is not None for c in conns)
-    slots, uspaces, sexp, arrays, _ = _routed_arrays(router, datagrams, general)
-    route_b, walked, longs = _crypto.receive_routed(
+    slots, uspaces, sexp, arrays, _, nxt = _routed_arrays_next(router, datagrams, general, next_phase)
+    closed = bytes(bool(c is not None and c.closed) for c in conns)
+    if nxt is None:
+        route_b, walked, longs = _crypto.receive_routed(
+            slots.table, router.map, router.host_cid_length, datagrams, *arrays, ReceivedPacket,
+            QuicPacketType.ONE_RTT, Epoch.ONE_RTT, closed, 0 if general else 1)
+        return _routed_finish(router, datagrams, slots, uspaces, sexp, route_b, walked, longs)
+    upairs, pnext = nxt
+    route_b, walked, longs = _crypto.receive_routed_phase(
         slots.table, router.map, router.host_cid_length, datagrams, *arrays, ReceivedPacket,
-        QuicPacketType.ONE_RTT, Epoch.ONE_RTT, bytes(bool(c is not None and c.closed) for c in conns),
-        0 if general else 1)
-    return _routed_finish(router, datagrams, slots, uspaces, sexp, route_b, walked, longs)
+        QuicPacketType.ONE_RTT, Epoch.ONE_RTT, closed, 1, pnext.tobytes())
+    if walked is None:
+        # a long header reached a connection after all (the host asked the router's own dict, so
+        # this is not expected): no state has moved, and the batch runs again without next slots
+        return receive_routed(router, datagrams)
+    rolled = walked[4]
+    return _routed_finish(router, datagrams, slots, uspaces, sexp, route_b, walked[:4], longs,
+                          [upairs[k] for k, f in enumerate(rolled) if f])
 
 
 def _routed_arrays(router, datagrams: list, general: bool):
+    """_routed_arrays_next without next-phase slots, and without its last item."""
+    return _routed_arrays_next(router, datagrams, general, False)[:5]
+
+
+def _routed_arrays_next(router, datagrams: list, general: bool, next_phase: bool):
     """What the fused calls of receive_routed and accept_routed take besides
     the datagrams: every key the batch can need is given a slot here, in one
     assign().  Returns (slots, the distinct 1-RTT spaces, their expected
     numbers, the packed per-connection arrays in _crypto.receive_routed's
-    order, the DCIDs of the batch's long headers or None)."""
+    order, the DCIDs of the batch's long headers or None, and, only when the
+    batch runs with next-phase slots (receive_routed, next_phase=True), the
+    distinct 1-RTT pairs and a next-phase slot or SLOT_NONE for each (plus the
+    keyless extra one), else None)."""
     conns = router.conns
     pix: dict = {}
     six: dict = {}
@@ -587,17 +625,34 @@ def _routed_arrays(router, datagrams: list, general: bool):
         extra = {id(p): p for ks in sets.values() for p in ks if p is not None and p.recv.aead is not None}
         xp = [p for k, p in extra.items() if k not in pix]
     got: list = []
+    # next-phase slots: not on the general path, and not when a long header
+    # reaches a known connection (_routed_long's walk does not know the rule)
+    pnext = None
+    if next_phase and not general and not touched and keyed:
+        pnext = np.full(len(upairs) + 1, 0xFFFFFFFF, np.uint32)
     if keyed or xp:
         # one assign() for the whole batch: a refill must not take an earlier slot away
         rc = [upairs[k].recv for k in keyed] + [p.recv for p in xp]
-        try:
-            got = slots.assign([(c.aead, c.hp, c.key_phase) for c in rc])
-        except OverflowError:
-            if not xp:
-                raise
-            # the table cannot hold these key-sets beside the 1-RTT ones: the general path
-            dcids, xp = None, []
-            got = slots.assign([(c.aead, c.hp, c.key_phase) for c in rc[:len(keyed)]])
+        triples = [(c.aead, c.hp, c.key_phase) for c in rc]
+        if pnext is not None:
+            # the next phase's AEAD key under the current HP key, with the other phase bit
+            ahead = [cached_next_phase(upairs[k].recv) for k in keyed]
+            try:
+                got = slots.assign(triples + [(a.aead, upairs[k].recv.hp, a.key_phase) for a, k in zip(ahead, keyed)])
+                pnext[keyed] = got[len(triples):]
+                got = got[:len(triples)]
+            except OverflowError:
+                # the table cannot hold the next slots beside the batch's keys: without them
+                pnext = None
+        if pnext is None:
+            try:
+                got = slots.assign(triples)
+            except OverflowError:
+                if not xp:
+                    raise
+                # the table cannot hold these key-sets beside the 1-RTT ones: the general path
+                dcids, xp = None, []
+                got = slots.assign(triples[:len(keyed)])
         pslot[keyed] = got[:len(keyed)]
     sexp = np.asarray([sp.expected_packet_number & 0xFFFFFFFFFFFFFFFF for sp in uspaces] + [0], np.uint64)
     a_pair = np.asarray(c_pair, np.int64)
@@ -629,11 +684,13 @@ def _routed_arrays(router, datagrams: list, general: bool):
                     ke_arr[c, j] = sp[e].expected_packet_number & 0xFFFFFFFFFFFFFFFF
         kslot, kexp = ks_arr.tobytes(), ke_arr.tobytes()
     return slots, uspaces, sexp, (a_pair.astype(np.uint32).tobytes(), a_space.astype(np.uint32).tobytes(),
-                                  pslot.tobytes(), sexp.tobytes(), kslot, kexp), dcids
+                                  pslot.tobytes(), sexp.tobytes(), kslot, kexp), dcids, \
+        None if pnext is None else (upairs, pnext)
 
 
-def _routed_finish(router, datagrams: list, slots, uspaces, sexp, route_b, walked, longs):
-    """receive_routed from what its fused call returned."""
+def _routed_finish(router, datagrams: list, slots, uspaces, sexp, route_b, walked, longs, rolled=()):
+    """receive_routed from what its fused call returned; `rolled`: the pairs
+    whose keys a packet of the batch updated (next_phase)."""
     conns = router.conns
     route = np.frombuffer(route_b, dtype=L.ROUTE)
     cls, rconn = route["cls"], route["conn"]
@@ -655,6 +712,10 @@ def _routed_finish(router, datagrams: list, slots, uspaces, sexp, route_b, walke
     for k, f in enumerate(closed):
         if f and conns[k] is not None:
             conns[k].closed = True
+    for pair in rolled:
+        # both directions, as _update_key does; the receive one adopts the
+        # cached context, whose slot then is the current one as it stands
+        pair._update_key_cached("remote_update")
     if deferred:
         # key-phase flips and numbers decoded under a stale expected number:
         # the general walk takes them in order from the state left above

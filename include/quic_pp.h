@@ -75,7 +75,8 @@ extern "C" {
 #define QPP_S_LENGTH 1      /* "Invalid payload length" (_crypto.c:126-129,168-171) or sample out of range */
 #define QPP_S_DECRYPT 2     /* "Payload decryption failed" (_crypto.c:148-152) */
 #define QPP_S_KEY_PHASE 3   /* short header whose key-phase bit differs from the slot's
-                               (quic/crypto.py:91-96): caller retries with the next-phase key */
+                               (quic/crypto.py:91-96): caller retries with the next-phase key,
+                               unless qpp_route_phase pointed the descriptor at it beforehand */
 #define QPP_S_NO_KEY 4      /* slot never installed: KeyUnavailableError (quic/crypto.py:78-79) */
 #define QPP_S_INTERNAL 5    /* the engine gave up on the packet: a bounded wait inside a kernel
                                (a GHASH table entry, a two-wave hand-over) ran out.  Nothing at
@@ -536,6 +537,45 @@ int qpp_route_accept(const uint64_t *d_off, const uint32_t *d_len, uint32_t n, c
  * library loaded).  Diagnostic: a batch without candidates makes none. */
 uint64_t qpp_route_accept_launches(void);
 
+/* qpp_route_phase: a peer's key update (quic/crypto.py:91-96, :184-192)
+ * resolved on the device ahead of the unprotect.  Asynchronous on `stream`;
+ * runs after qpp_route (and qpp_route_walk) on the same stream, over the
+ * d_desc[0, n) and d_route they wrote, and before qpp_unprotect.  d_next names
+ * a next-phase key slot, or QPP_SLOT_NONE, per connection: lane i consults
+ * S1 = d_next[d_route[i].conn], or, with d_route NULL, S1 = d_next[i] (one
+ * entry per descriptor; n_next is not looked at then).  One lane per
+ * descriptor.  The lane acts only if all of these hold; otherwise d_desc[i]
+ * is left untouched and d_phase[i] = 0:
+ *   - with route records, d_route[i].cls == QPP_R_SHORT and conn < n_next;
+ *   - QPP_F_NO_HP is not set in the descriptor's flags;
+ *   - 1 <= hdr_len <= QPP_MAX_HDR - 4 and hdr_len + 20 <= len, the bounds the
+ *     packet kernels check, so a packet that would get QPP_S_LENGTH still does;
+ *   - S0 = d_desc[i].slot < capacity and is installed;
+ *   - S1 < capacity, is installed, has S0's suite and the other key_phase.
+ * It then computes mask = HP(S0's header-protection key, in[in_off + hdr_len +
+ * 4 .. + 20)) and b0 = in[in_off] ^ (mask[0] & 0x1f).  If bit 7 of b0 is clear
+ * and ((b0 >> 2) & 1) != S0's key_phase, d_desc[i].slot = S1 and d_phase[i] =
+ * 1; otherwise d_phase[i] = 0.  Only the slot field of a descriptor ever
+ * changes; d_phase is written whole, so the same input gives the same bytes.
+ * A lane reads byte in_off and the 16 sample bytes of its packet, never a
+ * byte at or past in_off + len.
+ * The caller's contract: a next-phase slot holds the CURRENT slot's
+ * header-protection key (a key update keeps it, quic/crypto.py:157-168), the
+ * next phase's AEAD key and IV, and the opposite key_phase, so both slots give
+ * the same header mask and the packet kernels meet a slot whose phase matches
+ * the packet.  A next slot with another HP key only makes the re-pointed
+ * packet fail its tag (QPP_S_DECRYPT), which is harmless.  What a re-pointed
+ * packet's QPP_S_OK means for the connection's keys (CryptoPair._update_key) is
+ * the caller's, from d_phase.
+ * QPP_E_ARG: NULL kt, or a NULL d_next / d_desc / d_in / d_phase with n > 0.
+ * n == 0 returns QPP_OK and launches nothing. */
+int qpp_route_phase(const qpp_keytab *kt, const qpp_route_rec *d_route /* may be NULL */,
+                    const uint32_t *d_next, uint32_t n_next, qpp_desc *d_desc, uint32_t n,
+                    const uint8_t *d_in, uint8_t *d_phase, void *stream);
+/* qpp_route_phase launches of the resolving kernel (process-wide, since the
+ * library loaded).  Diagnostic: a batch with no next-phase slot makes none. */
+uint64_t qpp_route_phase_launches(void);
+
 /* Header-protection masks: replaces HeaderProtection_mask (_crypto.c:278-287).
  * d_samples: n x 16 bytes, d_masks: n x 16 bytes (first 5 used). */
 int qpp_hp_mask(const qpp_keytab *kt, const uint32_t *d_slots, const uint8_t *d_samples,
@@ -592,6 +632,31 @@ int qpp_session_route_walk_unprotect(qpp_session *s, const qpp_keytab *kt, const
                                      uint16_t desc_flags, uint8_t *out, size_t out_len, qpp_desc *desc_out,
                                      qpp_route_rec *route_out, qpp_result *res, qpp_walk_rec *walk_out,
                                      uint32_t *walk_n_out);
+/* qpp_session_route_walk_unprotect with the peers' key updates resolved on
+ * the device (qpp_route_phase) between the walk and the unprotect.
+ * conn_next[n_conn] (may be NULL) names each connection's next-phase 1-RTT
+ * slot or QPP_SLOT_NONE; phase_out[n] (required when conn_next is given)
+ * receives d_phase.  The sequence is one H2D, the routing kernel, the walking
+ * kernel when n_long > 0, the resolving kernel over descriptors [0, n) when
+ * conn_next holds at least one slot, one unplanned unprotect over n + 3
+ * n_long descriptors, one D2H; conn_next and phase_out ride in the same
+ * scratch copy in each direction.  The walk's extra descriptors [n, n + 3
+ * n_long) -- coalesced 1-RTT packets behind long headers, which exist only
+ * during a handshake, when no key update is legal -- are not resolved: a
+ * flipped one reports QPP_S_KEY_PHASE as ever.
+ * Checked on the host before anything is launched, besides what the walk form
+ * checks: every conn_next entry < capacity or QPP_SLOT_NONE, phase_out given
+ * with conn_next.  A violation is QPP_E_ARG and nothing is touched.  With
+ * conn_next NULL or all QPP_SLOT_NONE the call makes the same launches and
+ * returns the same bytes as qpp_session_route_walk_unprotect, and phase_out
+ * (if given) is zeros. */
+int qpp_session_route_phase_unprotect(qpp_session *s, const qpp_keytab *kt, const qpp_cidmap *m, uint32_t cid_len,
+                                      const uint64_t *off, const uint32_t *len, uint32_t n, const uint8_t *in,
+                                      size_t in_len, const uint32_t *long_idx, uint32_t n_long,
+                                      const uint32_t *conn_slot, const uint64_t *conn_expected, uint32_t n_conn,
+                                      const uint32_t *conn_next, uint16_t desc_flags, uint8_t *out, size_t out_len,
+                                      qpp_desc *desc_out, qpp_route_rec *route_out, qpp_result *res,
+                                      qpp_walk_rec *walk_out, uint32_t *walk_n_out, uint8_t *phase_out);
 /* qpp_session_route_walk_unprotect for a server that also takes on new
  * connections: between the walk and the unprotect, qpp_route_accept picks
  * the unrouted Initials among the candidates acc_row[n_acc] (rows of

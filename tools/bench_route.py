@@ -12,6 +12,9 @@ suites) in random arrival order, for n = 1 Mi and 64 Ki.
              bucket + unprotect       qpp_plan_build + qpp_unprotect_planned of
                                       those descriptors (the launch k_route feeds)
              unprotect alone          the planned launch without the plan build
+             k_phase                  (--next-phase) the key-phase resolution between
+                                      the two, every lane computing its mask and
+                                      none finding an update
   host     from a list of bytes, wall time, per n of --host-sizes:
              receive_routed           one call: stage, route + unprotect, walk
              dict + receive_datagrams a Python routing pass (data[1:9] dict
@@ -27,6 +30,22 @@ suites) in random arrival order, for n = 1 Mi and 64 Ki.
            ways: receive_routed (the device walks the long headers in the one
            fused call) against a Python routing pass (DCID dict lookup) and
            receive_datagrams of the items (the header walk in Python).
+
+  --next-phase   also time receive_routed(..., next_phase=True): every keyed
+           connection gets a slot for its next key phase and a kernel ahead of
+           the unprotect resolves the peers' key updates (qpp_route_phase).
+           The host part then alternates three ways and reports what the extra
+           kernel and the doubled slots cost a batch without an update
+           ("receive_routed_next_phase"), its first call (which builds every
+           connection's next-phase context) on its own, and that build timed
+           alone.  And a key-update workload (--update n datagrams, default
+           65536, over --update-conns connections, default 1024): every
+           connection's packets in order, each connection moving to its next
+           key phase at its midpoint, through receive_routed with next_phase
+           off (every flipped packet and all that follow it go through
+           ReceiveBatch), on with the next-phase contexts built inside the
+           call ("cold": the first batch after an update) and on with them
+           built before ("warm").  Every round starts from the first phase.
 
 The ways alternate in one process after --warmup rounds; median, min and max
 of --runs rounds.  Every round starts from the same connection state (expected
@@ -196,12 +215,116 @@ def connect_burst(n, C, runs, warmup):
     }, bool(eq)
 
 
+def key_update(n, C, runs, warmup):
+    """Every connection updates its keys once mid-batch -> (numbers, records equal)."""
+    from aioquic_amd import batch_io
+    from aioquic_amd import receive as R
+    from aioquic_amd.crypto import CryptoContext, CryptoPair, apply_key_phase, cached_next_phase, next_key_phase
+    from aioquic_amd.packet import QuicProtocolVersion
+    from aioquic_amd.route import CidRouter
+    from aioquic_amd.tls import CipherSuite, Epoch
+
+    rng = np.random.default_rng(0x4B55)
+    version = int(QuicProtocolVersion.VERSION_1)
+    suites = [(CipherSuite.AES_128_GCM_SHA256, 32), (CipherSuite.AES_256_GCM_SHA384, 48),
+              (CipherSuite.CHACHA20_POLY1305_SHA256, 32)]
+    batch_io._per_thread.slots = batch_io.KeySlots(4 * C)
+    send_slots = batch_io.KeySlots(2 * C)
+    cid = rng.integers(0, 256, (C, 8), dtype=np.uint8)
+    cid[:, :4] = np.arange(C, dtype=">u4").view(np.uint8).reshape(C, 4)  # distinct
+    cids = [cid[c].tobytes() for c in range(C)]
+    conns, first, senders = [], [], []
+    for c in range(C):
+        cs, slen = suites[c % 3]
+        secret = rng.bytes(slen)
+        pair = CryptoPair()
+        pair.recv.setup(cipher_suite=cs, secret=secret, version=version)
+        pair.send.setup(cipher_suite=cs, secret=secret[::-1], version=version)
+        conns.append(R.ConnectionKeys(cryptos={Epoch.ONE_RTT: pair}, spaces={Epoch.ONE_RTT: Space()},
+                                      host_cid_length=8))
+        # the first phase of both directions, to return to before every round
+        keep = []
+        for ctx in (pair.recv, pair.send):
+            k = CryptoContext()
+            k.aead, k.key_phase, k.secret = ctx.aead, ctx.key_phase, ctx.secret
+            keep.append(k)
+        first.append(keep)
+        peer = CryptoPair()
+        peer.send.setup(cipher_suite=cs, secret=secret, version=version)
+        # the peer's next phase: the next AEAD key under the header-protection key it keeps
+        nxt = next_key_phase(peer.send)
+        second = CryptoContext(key_phase=nxt.key_phase)
+        second.aead, second.hp = nxt.aead, peer.send.hp
+        senders.append((peer.send, second))
+    per = max(n // C, 2)
+    order = np.repeat(np.arange(C), per)
+    rng.shuffle(order)
+    sb = batch_io.SendBatch(slots=send_slots)
+    pn = [0] * C
+    for c in order.tolist():
+        ctx = senders[c][pn[c] >= per // 2]
+        h = bytes([0x41 | ctx.key_phase << 2]) + cids[c] + pn[c].to_bytes(2, "big")
+        sb.add(ctx, h, rng.bytes(1200 - len(h) - 16), pn[c])
+        pn[c] += 1
+    datagrams = sb.flush()
+    assert all(len(d) == 1200 for d in datagrams)
+    router = CidRouter(8, C)
+    for c, conn in enumerate(conns):
+        router.add(cids[c], conn)
+    pairs = [conn.cryptos[Epoch.ONE_RTT] for conn in conns]
+
+    def reset(warm):
+        for conn, pair, keep in zip(conns, pairs, first):
+            conn.spaces[Epoch.ONE_RTT].expected_packet_number = 0
+            for ctx, k in zip((pair.recv, pair.send), keep):
+                if ctx.aead is not k.aead:
+                    apply_key_phase(ctx, k, "reset")
+        if warm:
+            for pair in pairs:
+                cached_next_phase(pair.recv)
+        else:
+            for pair in pairs:
+                pair.recv._drop_next()
+
+    ways = (("next_phase_off", False, False), ("next_phase_on_cold", True, False), ("next_phase_on_warm", True, True))
+    times = {name: [] for name, _, _ in ways}
+    recs = {}
+    for r in range(warmup + runs):
+        for name, on, warm in ways:
+            reset(warm)
+            t0 = time.perf_counter()
+            got, unrouted = R.receive_routed(router, datagrams, next_phase=on)
+            t1 = time.perf_counter()
+            if r >= warmup:
+                times[name].append((t1 - t0) * 1e3)
+            assert not unrouted
+            if r + 1 == warmup + runs:
+                recs[name] = got
+            del got
+    phases = {pair.recv.key_phase for pair in pairs}
+    nd = len(datagrams)
+    eq = phases == {1} and all(len(v) == nd and all(g.dropped is None for g in v) for v in recs.values()) and \
+        recs["next_phase_off"] == recs["next_phase_on_cold"] == recs["next_phase_on_warm"]
+    out = {"datagrams": nd, "connections": C, "updates": C, "same_records": bool(eq)}
+    for name, _, _ in ways:
+        m = statistics.median(times[name])
+        out[name] = dict(_stats(times[name]), datagrams_per_s=round(nd / (m * 1e-3)))
+    off = statistics.median(times["next_phase_off"])
+    out["off_over_on_cold"] = round(off / statistics.median(times["next_phase_on_cold"]), 3)
+    out["off_over_on_warm"] = round(off / statistics.median(times["next_phase_on_warm"]), 3)
+    return out, bool(eq)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--conns", type=int, default=4096)
     ap.add_argument("--sizes", default="1048576,65536", help="datagrams per batch, device part")
     ap.add_argument("--host-sizes", default="1048576,65536", help="datagrams per batch, host part ('' = skip)")
     ap.add_argument("--burst", type=int, default=65536, help="datagrams of the connect-burst mix (0 = skip)")
+    ap.add_argument("--next-phase", action="store_true",
+                    help="also time receive_routed(..., next_phase=True), and the key-update workload")
+    ap.add_argument("--update", type=int, default=65536, help="datagrams of the key-update workload (0 = skip)")
+    ap.add_argument("--update-conns", type=int, default=1024, help="connections of the key-update workload")
     ap.add_argument("--runs", type=int, default=11)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--timeout", type=int, default=900, help="seconds before the run gives up")
@@ -218,7 +341,7 @@ def main():
     from aioquic_amd import receive as R
     from aioquic_amd.batch import PacketEngine
     from aioquic_amd.bench_data import HDR_LEN, SLOT_BYTES, make_workload
-    from aioquic_amd.crypto import CryptoPair, derive_key_iv_hp
+    from aioquic_amd.crypto import CryptoPair, cached_next_phase, derive_key_iv_hp
     from aioquic_amd.packet import QuicProtocolVersion
     from aioquic_amd.route import CidRouter
     from aioquic_amd.tls import CipherSuite, Epoch
@@ -241,8 +364,15 @@ def main():
         secrets.append((cs, secret))
         key, iv, hp = derive_key_iv_hp(cipher_suite=cs, secret=secret, version=version)
         keys[c] = L.key_material(c, suite, key, iv, hp)[0]
-    eng = PacketEngine(C)
+    eng = PacketEngine(2 * C if a.next_phase else C)
     eng.set_key_records(keys)
+    if a.next_phase:
+        # a next-phase slot per connection at C + c: the same HP key, the other phase bit (the AEAD
+        # key does not matter: the traffic carries no update, so k_phase re-points nothing)
+        ahead = keys.copy()
+        ahead["slot"] += C
+        ahead["key_phase"] = 1
+        eng.set_key_records(ahead)
     cmap = eng.cid_map(C)
     cmap.put(np.concatenate([L.cid_entry(x, c) for c, x in enumerate(cids)]).tobytes())
 
@@ -270,7 +400,7 @@ def main():
         e1.synchronize()
         return e0.elapsed_time(e1)
 
-    out = {"tool": "bench_route", "connections": C, "datagram_bytes": SLOT_BYTES, "runs": a.runs,
+    out = {"tool": "bench_route", "next_phase": bool(a.next_phase), "connections": C, "datagram_bytes": SLOT_BYTES, "runs": a.runs,
            "warmup": a.warmup, "map_buckets": cmap.buckets, "device": {}, "host": {}}
     host_sizes = [int(x) for x in a.host_sizes.split(",") if x]
     wires = {}
@@ -291,9 +421,17 @@ def main():
         both = lambda: eng.unprotect(d_desc, n, d_wire, d_out, d_res, plan=eng.bucket(d_desc, n))
         plan = [None]
         alone = lambda: eng.unprotect(d_desc, n, d_wire, d_out, d_res, plan=plan[0])
-        t_route, t_both, t_alone = [], [], []
+        t_route, t_both, t_alone, t_phase = [], [], [], []
+        if a.next_phase:
+            d_next = t(np.arange(C, 2 * C, dtype=np.uint32))
+            d_phase = torch.full((n,), 0xAB, dtype=torch.uint8, device=dev)
+            phase = lambda: eng.route_phase(d_route, d_next, C, d_desc, n, d_wire, d_phase)
         for r in range(a.warmup + a.runs):
             x = timed(route)
+            if a.next_phase:
+                p_ = timed(phase)
+                if r >= a.warmup:
+                    t_phase.append(p_)
             y = timed(both)
             plan[0] = eng.bucket(d_desc, n)
             z = timed(alone)
@@ -314,6 +452,12 @@ def main():
             "k_route_gb_per_s_at_200B": round(200 * n / (mr * 1e-3) / 1e9, 1),
             "routed_and_unprotected_ok": ok,
         }
+        if a.next_phase:
+            mp = statistics.median(t_phase)
+            ok = ok and not d_phase.cpu().numpy().any()
+            out["device"][str(n)]["k_phase"] = dict(_stats(t_phase), over_k_route=round(mp / mr, 3),
+                                                   over_planned_unprotect=round(mp / mb, 4),
+                                                   ns_per_datagram=round(mp * 1e6 / n, 3))
         if not ok:
             print(json.dumps(out))
             sys.exit("bench_route: the routed batch did not unprotect")
@@ -337,6 +481,11 @@ def main():
         for conn in conns:
             conn.spaces[Epoch.ONE_RTT].expected_packet_number = 0
 
+    if a.next_phase and host_sizes:
+        # a slot for every connection's next phase beside its current one
+        from aioquic_amd import batch_io
+
+        batch_io._per_thread.slots = batch_io.KeySlots(2 * C + 64)
     same = True
     for n in host_sizes:
         if n not in wires:
@@ -346,9 +495,35 @@ def main():
         raw = wire[: n * SLOT_BYTES].tobytes()
         datagrams = [raw[i * SLOT_BYTES:(i + 1) * SLOT_BYTES] for i in range(n)]
         del raw, wire
-        t_routed, t_dict, t_pass = [], [], []
+        t_routed, t_dict, t_pass, t_next = [], [], [], []
         got = want = None
+        first_next = build_next = None
+        same_next = True
+        if a.next_phase:
+            # the first call with next slots builds every connection's next-phase context
+            for conn in conns:
+                conn.cryptos[Epoch.ONE_RTT].recv._drop_next()
+            reset()
+            t0 = time.perf_counter()
+            ahead, _ = R.receive_routed(router, datagrams, next_phase=True)
+            first_next = (time.perf_counter() - t0) * 1e3
+            del ahead
+            for conn in conns:
+                conn.cryptos[Epoch.ONE_RTT].recv._drop_next()
+            t0 = time.perf_counter()
+            for conn in conns:
+                cached_next_phase(conn.cryptos[Epoch.ONE_RTT].recv)
+            build_next = (time.perf_counter() - t0) * 1e3
         for r in range(a.warmup + a.runs):
+            if a.next_phase:
+                reset()
+                t0 = time.perf_counter()
+                ahead, unrouted = R.receive_routed(router, datagrams, next_phase=True)
+                t1 = time.perf_counter()
+                if r >= a.warmup:
+                    t_next.append((t1 - t0) * 1e3)
+                if r + 1 < a.warmup + a.runs:
+                    del ahead
             reset()
             t0 = time.perf_counter()
             got, unrouted = R.receive_routed(router, datagrams)
@@ -376,9 +551,21 @@ def main():
             "dict_way_over_routed": round(md / mr, 3),
             "same_records": bool(eq),
         }
+        if a.next_phase:
+            same_next = ahead == got
+            same = same and same_next
+            mn = statistics.median(t_next)
+            out["host"][str(n)]["receive_routed_next_phase"] = dict(
+                _stats(t_next), datagrams_per_s=round(n / (mn * 1e-3)), over_default=round(mn / mr, 4),
+                first_call_ms=round(first_next, 3), next_contexts_build_ms=round(build_next, 3),
+                same_records=bool(same_next))
+            del ahead
         del datagrams, got, want
     if a.burst:
         out["connect_burst"], eq = connect_burst(a.burst, C, a.runs, a.warmup)
+        same = same and eq
+    if a.next_phase and a.update:
+        out["key_update"], eq = key_update(a.update, a.update_conns, a.runs, a.warmup)
         same = same and eq
     line = json.dumps(out)
     print(line)
