@@ -177,6 +177,23 @@ class PacketEngine:
                              _ptr(walk), _ptr(walk_n), _ptr(acc_row), _ptr(acc_slot), int(n_acc), int(accept_flags),
                              int(flags), _ptr(ini), _ptr(desc), _ptr(acc), self._stream(stream))
 
+    @staticmethod
+    def route_reply(offs, lens, n: int, inbuf, long_idx, n_long: int, walk, acc_row, acc, n_acc: int, addr, rand,
+                    token_ctr: int, versions, reply_flags: int, reply, seal, tag, rec, stream=None) -> None:
+        """qpp_route_reply on device buffers, after route_accept() on the same
+        stream: the Version Negotiation (RP_VN) and Retry (RP_RETRY) packets
+        for the candidates the device did not accept, assembled into `reply`
+        (REPLY_STRIDE bytes per candidate) with REPLY records (`rec`) and two
+        DESC arrays: `seal` and then `tag` go through protect() of the reply
+        key table, in place in `reply`, to seal the tokens and append the
+        integrity tags.  `addr` (20 bytes per candidate; None without
+        RP_RETRY) and `rand` (16 per candidate) are uint8 device buffers,
+        `versions` a host sequence of 1..16 version numbers."""
+        _crypto.route_reply(_ptr(offs), _ptr(lens), int(n), _ptr(inbuf), _ptr(long_idx), int(n_long), _ptr(walk),
+                            _ptr(acc_row), _ptr(acc), int(n_acc), 0 if addr is None else _ptr(addr), _ptr(rand),
+                            int(token_ctr), np.asarray(versions, np.uint32).tobytes(), int(reply_flags), _ptr(reply),
+                            _ptr(seal), _ptr(tag), _ptr(rec), PacketEngine._stream(stream))
+
     def route_walk_unprotect_host(self, cid_map, cid_len: int, offs, lens, data, long_idx, conn_slot,
                                   conn_expected, out_len: int, flags: int = 0):
         """Route, walk the long-header datagrams `long_idx` and unprotect a

@@ -35,6 +35,7 @@
  *   route_unprotect_host(table, map, cid_len, offs, lens, data, conn_slot, conn_expected,
  *                        flags, out_len) -> (out, desc, route, results)
  *   receive_routed(...)                             receive.receive_routed's C path
+ *   route_reply(...), receive_accept_reply(...)     Retry / Version Negotiation replies built on the device
  *   route_accept(...), receive_accept(...)          unrouted Initials accepted on the device:
  *                                                   the device form, receive.accept_routed's C path
  *
@@ -1355,6 +1356,37 @@ static PyObject *py_route_accept_launches(PyObject *m, PyObject *unused)
     return PyLong_FromUnsignedLongLong(qpp_route_accept_launches());
 }
 
+/* route_reply(off_ptr, len_ptr, n, in_ptr, long_ptr, n_long, walk_ptr, row_ptr, acc_ptr, n_acc, addr_ptr, rand_ptr,
+ *             token_ctr, versions_u32, reply_flags, reply_ptr, seal_ptr, tag_ptr, rec_ptr, stream) */
+static PyObject *py_route_reply(PyObject *m, PyObject *args)
+{
+    unsigned long long op, lp, ip, xp, wp, arp, accp, adp, rnp, ctr, rep, sealp, tagp, recp, sp;
+    unsigned int n, n_long, n_acc, reply_flags;
+    const char *vers;
+    Py_ssize_t l_vers;
+    if (!PyArg_ParseTuple(args, "KKIKKIKKKIKKKy#IKKKKK", &op, &lp, &n, &ip, &xp, &n_long, &wp, &arp, &accp, &n_acc, &adp,
+                          &rnp, &ctr, &vers, &l_vers, &reply_flags, &rep, &sealp, &tagp, &recp, &sp))
+        return NULL;
+    int rc = l_vers % 4 || l_vers > 4 * QPP_RP_MAX_VERSIONS
+                 ? QPP_E_ARG
+                 : qpp_route_reply(as_ptr(op), as_ptr(lp), n, as_ptr(ip), as_ptr(xp), n_long, as_ptr(wp), as_ptr(arp),
+                                   as_ptr(accp), n_acc, as_ptr(adp), as_ptr(rnp), ctr, (const uint32_t *)vers,
+                                   (uint32_t)(l_vers / 4), reply_flags, as_ptr(rep), as_ptr(sealp), as_ptr(tagp),
+                                   as_ptr(recp), as_ptr(sp));
+    if (rc == QPP_E_ARG) {
+        PyErr_SetString(PyExc_ValueError, "bad route_reply arguments (a null buffer, an unknown reply flag, or not "
+                                          "1..16 versions)");
+        return NULL;
+    }
+    if (check_rc(rc) < 0) return NULL;
+    Py_RETURN_NONE;
+}
+
+static PyObject *py_route_reply_launches(PyObject *m, PyObject *unused)
+{
+    return PyLong_FromUnsignedLongLong(qpp_route_reply_launches());
+}
+
 static int host_call(int enc, qpp_keytab *kt, const void *desc, uint32_t n, const void *in,
                      size_t in_len, void *out, size_t out_len, void *res)
 {
@@ -2490,6 +2522,15 @@ done:
  * holds the packed qpp_accept_rec, 2 x qpp_key_material and 2 x 32 secret
  * bytes of every candidate.
  *
+ * receive_accept_reply(the arguments of receive_accept, reply_table, addr, rand, token_ctr, versions_u32,
+ *                      reply_flags)
+ *     -> (route, None, None | (...), (accept records, key material, secrets), (reply buffer, reply records))
+ * receive_accept for a server that also answers what it does not accept
+ * (asyncio/server.py:71-111): the call is qpp_session_accept_reply_unprotect.
+ * addr holds 20 bytes per candidate (or is empty without QPP_RP_RETRY), rand
+ * 16; the fifth item holds the 256 bytes and the packed qpp_reply_rec of
+ * every candidate (zeros when no reply flag is set).
+ *
  * receive_routed_phase(the arguments of receive_routed, pair_next_u32)
  *     -> (route, None | (records, deferred, space_exp after, conn_closed after, pair_rolled_u8), None | (...))
  * receive_routed with the peers' key updates resolved on the device: the call
@@ -2506,14 +2547,23 @@ done:
  * may be empty when no datagram starts with a long header. */
 static PyObject *receive_routed_impl(PyObject *args, int mode)
 {
-    const int accept = mode == 1, phased = mode == 2;
+    const int reply = mode == 3, accept = mode == 1 || reply, phased = mode == 2;
     PyObject *t, *mo, *dgs, *rec_type, *ptype, *epoch;
     const char *a_pair, *a_space, *a_pslot, *a_sexp, *a_closed, *a_kslot, *a_kexp, *a_arow = NULL, *a_aslot = NULL;
     const char *a_pnext = NULL;
     Py_ssize_t l_pair, l_space, l_pslot, l_sexp, l_closed, l_kslot, l_kexp, l_arow = 0, l_aslot = 0, l_pnext = 0;
-    unsigned int cid_len, accept_flags = 0;
+    unsigned int cid_len, accept_flags = 0, reply_flags = 0;
+    unsigned long long token_ctr = 0;
+    PyObject *rt = NULL;
+    const char *a_addr = NULL, *a_rand = NULL, *a_vers = NULL;
+    Py_ssize_t l_addr = 0, l_rand = 0, l_vers = 0;
     int walk;
-    if (!(accept ? PyArg_ParseTuple(args, "OOIO!y#y#y#y#y#y#OOOy#iy#y#I", &t, &mo, &cid_len, &PyList_Type, &dgs, &a_pair,
+    if (!(reply ? PyArg_ParseTuple(args, "OOIO!y#y#y#y#y#y#OOOy#iy#y#IOy#y#Ky#I", &t, &mo, &cid_len, &PyList_Type, &dgs,
+                                   &a_pair, &l_pair, &a_space, &l_space, &a_pslot, &l_pslot, &a_sexp, &l_sexp, &a_kslot,
+                                   &l_kslot, &a_kexp, &l_kexp, &rec_type, &ptype, &epoch, &a_closed, &l_closed, &walk,
+                                   &a_arow, &l_arow, &a_aslot, &l_aslot, &accept_flags, &rt, &a_addr, &l_addr, &a_rand,
+                                   &l_rand, &token_ctr, &a_vers, &l_vers, &reply_flags)
+          : accept ? PyArg_ParseTuple(args, "OOIO!y#y#y#y#y#y#OOOy#iy#y#I", &t, &mo, &cid_len, &PyList_Type, &dgs, &a_pair,
                                     &l_pair, &a_space, &l_space, &a_pslot, &l_pslot, &a_sexp, &l_sexp, &a_kslot,
                                     &l_kslot, &a_kexp, &l_kexp, &rec_type, &ptype, &epoch, &a_closed, &l_closed, &walk,
                                     &a_arow, &l_arow, &a_aslot, &l_aslot, &accept_flags)
@@ -2529,6 +2579,8 @@ static PyObject *receive_routed_impl(PyObject *args, int mode)
     qpp_keytab *kt = as_table(t);
     qpp_cidmap *map = kt ? as_cidmap(mo) : NULL;
     if (!map) return NULL;
+    qpp_keytab *reply_kt = reply ? as_table(rt) : NULL;
+    if (reply && !reply_kt) return NULL;
     if (!PyType_Check(rec_type) || !PyType_IsSubtype((PyTypeObject *)rec_type, &PyTuple_Type)) {
         PyErr_SetString(PyExc_TypeError, "rec_type must be a tuple subclass");
         return NULL;
@@ -2566,6 +2618,11 @@ static PyObject *receive_routed_impl(PyObject *args, int mode)
                                           "the walk's arrays are required");
         return NULL;
     }
+    if (reply && ((l_addr && l_addr != QPP_RP_ADDR_STRIDE * na) || l_rand != QPP_RP_RAND_STRIDE * na || l_vers % 4)) {
+        PyErr_SetString(PyExc_ValueError, "addr: 20 bytes per candidate or none; rand: 16 bytes per candidate; "
+                                          "versions: whole u32 items");
+        return NULL;
+    }
     PyTypeObject *tp = (PyTypeObject *)rec_type;
     allocfunc alloc = (allocfunc)PyType_GetSlot(tp, Py_tp_alloc);
     if (!alloc) return NULL;
@@ -2594,6 +2651,7 @@ static PyObject *receive_routed_impl(PyObject *args, int mode)
     PyObject *ret = NULL, *route = NULL, *recs = NULL, *deferred = NULL, *sexp_out = NULL, *closed_out = NULL;
     PyObject *empty = NULL, *minus1 = NULL, *zero = NULL, *s_key = NULL, *s_dec = NULL, *s_rsv = NULL, *s_closed = NULL;
     PyObject *walked = NULL, *longs = NULL, *acc = NULL, *km = NULL, *secrets = NULL, *rolled_out = NULL;
+    PyObject *rbuf = NULL, *rrec = NULL;
     /* phased: the per-connection next-phase slots, the device's verdicts, and the walk form's arrays when
        the caller gave none (a batch with no long header) */
     uint32_t *cnext = NULL, *ks_own = NULL;
@@ -2614,6 +2672,14 @@ static PyObject *receive_routed_impl(PyObject *args, int mode)
         km = PyBytes_FromStringAndSize(NULL, na * 2 * (Py_ssize_t)sizeof(qpp_key_material));
         secrets = PyBytes_FromStringAndSize(NULL, na * 64);
         if (!acc || !km || !secrets) goto nomem;
+    }
+    if (reply) {
+        /* zeros when the call makes no reply (no flag, no candidate) */
+        rbuf = PyBytes_FromStringAndSize(NULL, na * QPP_REPLY_STRIDE);
+        rrec = PyBytes_FromStringAndSize(NULL, na * (Py_ssize_t)sizeof(qpp_reply_rec));
+        if (!rbuf || !rrec) goto nomem;
+        memset(PyBytes_AsString(rbuf), 0, (size_t)na * QPP_REPLY_STRIDE);
+        memset(PyBytes_AsString(rrec), 0, (size_t)na * sizeof(qpp_reply_rec));
     }
     if (!offs || !cexp || !lens || !cslot || !conn_of || !slot_of || !dg || !lidx || !cd || !cs || !cl ||
         !blocked_pair || !blocked_space || !blocked_conn || !od || !os_ || !ol)
@@ -2672,7 +2738,16 @@ static PyObject *receive_routed_impl(PyObject *args, int mode)
         int rc;
         Py_BEGIN_ALLOW_THREADS  /* the snapshot holds every datagram */
         par_copy(cd, cs, cl, (size_t)n, total);
-        if (accept)
+        if (reply)
+            rc = qpp_session_accept_reply_unprotect(
+                ss, kt, map, cid_len, offs, lens, (uint32_t)n, hin, total, lidx, nl, (const uint32_t *)a_kslot,
+                (const uint64_t *)a_kexp, (uint32_t)nc, 0, (const uint32_t *)a_arow, (const uint32_t *)a_aslot,
+                (uint32_t)na, accept_flags, reply_kt, l_addr ? (const uint8_t *)a_addr : NULL, (const uint8_t *)a_rand,
+                token_ctr, (const uint32_t *)a_vers, (uint32_t)(l_vers / 4), reply_flags, hout, total, desc,
+                (qpp_route_rec *)rr, res, wrec, wn, (qpp_accept_rec *)PyBytes_AsString(acc),
+                (qpp_key_material *)PyBytes_AsString(km), (uint8_t *)PyBytes_AsString(secrets),
+                (uint8_t *)PyBytes_AsString(rbuf), (qpp_reply_rec *)PyBytes_AsString(rrec));
+        else if (accept)
             rc = qpp_session_accept_unprotect(ss, kt, map, cid_len, offs, lens, (uint32_t)n, hin, total, lidx, nl,
                                               (const uint32_t *)a_kslot, (const uint64_t *)a_kexp, (uint32_t)nc, 0,
                                               (const uint32_t *)a_arow, (const uint32_t *)a_aslot, (uint32_t)na,
@@ -2696,6 +2771,13 @@ static PyObject *receive_routed_impl(PyObject *args, int mode)
         if (phased && rc == QPP_E_ARG) {
             PyErr_SetString(PyExc_ValueError, "bad arguments (a next-phase slot outside the table); nothing was "
                                               "launched");
+            goto done;
+        }
+        if (reply && rc == QPP_E_ARG) {
+            PyErr_SetString(PyExc_ValueError, "bad accept or reply arguments (those of receive_accept, a reply table "
+                                              "of fewer than 3 slots, an address length that is neither 6 nor 18, "
+                                              "not 1..16 versions, an unknown reply flag, or a token counter that "
+                                              "wraps); nothing was launched");
             goto done;
         }
         if (accept && rc == QPP_E_ARG) {
@@ -2736,7 +2818,13 @@ static PyObject *receive_routed_impl(PyObject *args, int mode)
         }
         if (accept) {
             PyObject *found = PyTuple_Pack(3, acc, km, secrets);
-            if (found) ret = PyTuple_Pack(4, route, Py_None, longs ? longs : Py_None, found);
+            PyObject *sent = reply && found ? PyTuple_Pack(2, rbuf, rrec) : NULL;
+            if (found && reply) {
+                if (sent) ret = PyTuple_Pack(5, route, Py_None, longs ? longs : Py_None, found, sent);
+            } else if (found) {
+                ret = PyTuple_Pack(4, route, Py_None, longs ? longs : Py_None, found);
+            }
+            Py_XDECREF(sent);
             Py_XDECREF(found);
         } else {
             ret = PyTuple_Pack(3, route, Py_None, longs ? longs : Py_None);
@@ -2790,6 +2878,8 @@ done:
     Py_XDECREF(acc);
     Py_XDECREF(km);
     Py_XDECREF(secrets);
+    Py_XDECREF(rbuf);
+    Py_XDECREF(rrec);
     free(cd), free(cs), free(cl), free(blocked_pair), free(blocked_space), free(blocked_conn), free(od), free(os_);
     free(ol);
     Py_DECREF(dgs);
@@ -2812,6 +2902,7 @@ done:
 static PyObject *py_receive_routed(PyObject *m, PyObject *args) { return receive_routed_impl(args, 0); }
 static PyObject *py_receive_accept(PyObject *m, PyObject *args) { return receive_routed_impl(args, 1); }
 static PyObject *py_receive_routed_phase(PyObject *m, PyObject *args) { return receive_routed_impl(args, 2); }
+static PyObject *py_receive_accept_reply(PyObject *m, PyObject *args) { return receive_routed_impl(args, 3); }
 
 /* long_dcids(datagrams) -> None when no bytes object of the list starts with
  * a long header (first byte, bit 7), else the set of the destination CIDs of
@@ -2926,6 +3017,10 @@ static PyMethodDef module_methods[] = {
     {"receive_routed_phase", py_receive_routed_phase, METH_VARARGS,
      "receive_routed with a next-phase key slot per pair: peers' key updates resolved on the device"},
     {"route_accept_launches", py_route_accept_launches, METH_NOARGS, "qpp_route_accept_launches()"},
+    {"route_reply", py_route_reply, METH_VARARGS, "qpp_route_reply on device buffers"},
+    {"route_reply_launches", py_route_reply_launches, METH_NOARGS, "qpp_route_reply_launches()"},
+    {"receive_accept_reply", py_receive_accept_reply, METH_VARARGS,
+     "receive_accept that also builds the Retry / Version Negotiation replies on the device"},
     {"receive_accept", py_receive_accept, METH_VARARGS,
      "receive_routed with the unrouted Initials among the candidates accepted on the device "
      "(qpp_session_accept_unprotect)"},

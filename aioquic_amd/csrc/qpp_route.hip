@@ -1,7 +1,8 @@
 // qpp_route.hip -- routing received datagrams to connections by connection ID
 // on the device (quic_pp.h: qpp_cidmap_*, qpp_route, qpp_route_walk,
-// qpp_route_accept, qpp_session_route_unprotect,
-// qpp_session_route_walk_unprotect, qpp_session_accept_unprotect).
+// qpp_route_accept, qpp_route_reply, qpp_session_route_unprotect,
+// qpp_session_route_walk_unprotect, qpp_session_accept_unprotect,
+// qpp_session_accept_reply_unprotect).
 //
 // Replaces the per-datagram routing of the reference's server
 // (asyncio/server.py:60-152: pull_quic_header, then
@@ -20,6 +21,7 @@
 #include "quic_pp.h"
 #include "qpp_internal.h"
 #include "qpp_accept.h"
+#include "qpp_reply.h"
 #include "qpp_route.h"
 #include "qpp_walk.h"
 
@@ -44,6 +46,14 @@ static_assert(sizeof(qpp_accept_rec) == sizeof(qpp_ac::Acc) && sizeof(qpp_initia
               QPP_CONN_NONE == qpp_ac::kConnNone && QPP_R_LONG == qpp_ac::kClsLong &&
               QPP_DERIVE_V2 == qpp_ac::kDeriveV2 && QPP_CID_MAX == qpp_wk::kCidMax,
               "accept records");
+static_assert(sizeof(qpp_reply_rec) == sizeof(qpp_rp::Rec) && QPP_REPLY_STRIDE == qpp_rp::kStride &&
+              QPP_RP_MAX_VERSIONS == qpp_rp::kMaxVersions && QPP_RP_ADDR_STRIDE == qpp_rp::kAddrStride &&
+              QPP_RP_RAND_STRIDE == qpp_rp::kRandStride && QPP_RP_VN == qpp_rp::kVn &&
+              QPP_RP_RETRY == qpp_rp::kRetry && QPP_RP_KIND_NONE == qpp_rp::kKindNone &&
+              QPP_RP_KIND_VN == qpp_rp::kKindVn && QPP_RP_KIND_RETRY == qpp_rp::kKindRetry &&
+              QPP_RP_OK == qpp_rp::kStOk && QPP_RP_BOUNDS == qpp_rp::kBounds && QPP_RP_ADDR == qpp_rp::kAddr &&
+              QPP_F_NO_HP == qpp_rp::kNoHp && QPP_TAG_LEN == qpp_rp::kTagLen,
+              "reply records");
 
 struct qpp_cidmap {
     HostMap host;
@@ -309,8 +319,81 @@ __global__ __launch_bounds__(kRouteWG) void k_accept(const uint64_t *off, const 
     }
 }
 
+// The supported versions of a Version Negotiation reply, by value among the
+// kernel's arguments.
+struct ReplyVersions {
+    uint32_t v[QPP_RP_MAX_VERSIONS];
+};
+
+// One lane per candidate (k_reply): the assembly of
+// qpp_reply.h over the lane's own accept and walk records, into its own 256
+// bytes of the reply buffer, its two descriptors and its record.  No LDS, no
+// atomics: everything lane a writes is indexed by a.
+__global__ __launch_bounds__(kRouteWG) void k_reply(const uint64_t *off, const uint32_t *len, uint32_t n,
+                                                    const uint8_t *in, const uint32_t *long_idx, uint32_t n_long,
+                                                    const qpp_walk_rec *walk, const uint32_t *acc_row,
+                                                    const qpp_accept_rec *acc, uint32_t n_acc, const uint8_t *addr,
+                                                    const uint8_t *rnd, uint64_t token_ctr, ReplyVersions vs,
+                                                    uint32_t n_versions, uint32_t reply_flags, uint8_t *reply,
+                                                    qpp_desc *seal, qpp_desc *tag, qpp_reply_rec *rec)
+{
+    const uint32_t a = blockIdx.x * kRouteWG + threadIdx.x;
+    if (a >= n_acc) return;
+    const uint32_t r = acc_row[a];
+    const uint32_t i = r < n_long ? long_idx[r] : n;
+    // a row or an index outside the batch (not the caller's contract): no
+    // reply, and nothing of the batch is read
+    uint8_t st = QPP_ACC_NOT_INITIAL;
+    uint32_t l = 0;
+    uint64_t o = 0;
+    qpp_wk::Rec w0;
+    w0.off = w0.len = w0.version = w0.desc = 0;
+    w0.pn_off = w0.token_len = 0;
+    w0.type = w0.status = w0.dcid_len = w0.scid_len = 0;
+    if (i < n) {
+        st = acc[a].status;
+        o = off[i];
+        l = len[i];
+        const qpp_walk_rec q = walk[(size_t)r * QPP_WALK_MAX];
+        w0.version = q.version;
+        w0.dcid_len = q.dcid_len;
+        w0.scid_len = q.scid_len;
+    }
+    qpp_ac::Desc rs, rt;
+    qpp_rp::Rec rr;
+    qpp_rp::reply_one(a, st, w0, l, in + o, addr ? addr + (size_t)a * QPP_RP_ADDR_STRIDE : NULL,
+                      rnd + (size_t)a * QPP_RP_RAND_STRIDE, token_ctr, vs.v, n_versions, reply_flags,
+                      reply + (size_t)a * QPP_REPLY_STRIDE, rs, rt, rr);
+    qpp_desc d;
+    d.in_off = rs.in_off;
+    d.out_off = rs.out_off;
+    d.len = rs.len;
+    d.hdr_len = rs.hdr_len;
+    d.flags = rs.flags;
+    d.pn = rs.pn;
+    d.slot = rs.slot;
+    d.rsv = rs.rsv;
+    seal[a] = d;
+    d.in_off = rt.in_off;
+    d.out_off = rt.out_off;
+    d.len = rt.len;
+    d.hdr_len = rt.hdr_len;
+    d.flags = rt.flags;
+    d.pn = rt.pn;
+    d.slot = rt.slot;
+    d.rsv = rt.rsv;
+    tag[a] = d;
+    qpp_reply_rec q;
+    q.off = rr.off;
+    q.len = rr.len;
+    q.kind = rr.kind;
+    q.status = rr.status;
+    rec[a] = q;
+}
+
 std::atomic<uint64_t> g_walk_launches{0};
 std::atomic<uint64_t> g_accept_launches{0};
+std::atomic<uint64_t> g_reply_launches{0};
 
 void map_entries(const qpp_cid_entry *e, uint32_t n, std::vector<HostMap::Entry> &v)
 {
@@ -500,6 +583,31 @@ int qpp_route_accept(const uint64_t *d_off, const uint32_t *d_len, uint32_t n, c
 
 uint64_t qpp_route_accept_launches(void) { return g_accept_launches.load(std::memory_order_relaxed); }
 
+int qpp_route_reply(const uint64_t *d_off, const uint32_t *d_len, uint32_t n, const uint8_t *d_in,
+                    const uint32_t *d_long_idx, uint32_t n_long, const qpp_walk_rec *d_walk,
+                    const uint32_t *d_acc_row, const qpp_accept_rec *d_acc, uint32_t n_acc, const uint8_t *d_addr,
+                    const uint8_t *d_rand, uint64_t token_ctr, const uint32_t *versions, uint32_t n_versions,
+                    uint32_t reply_flags, uint8_t *d_reply, qpp_desc *d_seal, qpp_desc *d_tag, qpp_reply_rec *d_rec,
+                    void *stream)
+{
+    if (reply_flags & ~(QPP_RP_VN | QPP_RP_RETRY)) return QPP_E_ARG;
+    if (!versions || n_versions < 1 || n_versions > QPP_RP_MAX_VERSIONS) return QPP_E_ARG;
+    if (n_acc == 0) return QPP_OK;
+    if (!d_off || !d_len || !d_in || !d_long_idx || !d_walk || !d_acc_row || !d_acc || !d_rand || !d_reply ||
+        !d_seal || !d_tag || !d_rec || ((reply_flags & QPP_RP_RETRY) && !d_addr))
+        return QPP_E_ARG;
+    ReplyVersions vs;
+    for (uint32_t k = 0; k < QPP_RP_MAX_VERSIONS; ++k) vs.v[k] = k < n_versions ? versions[k] : 0;
+    hipLaunchKernelGGL(k_reply, dim3((n_acc + kRouteWG - 1) / kRouteWG), dim3(kRouteWG), 0, (hipStream_t)stream,
+                       d_off, d_len, n, d_in, d_long_idx, n_long, d_walk, d_acc_row, d_acc, n_acc, d_addr, d_rand,
+                       token_ctr, vs, n_versions, reply_flags, d_reply, d_seal, d_tag, d_rec);
+    HIPCHK(hipGetLastError());
+    g_reply_launches.fetch_add(1, std::memory_order_relaxed);
+    return QPP_OK;
+}
+
+uint64_t qpp_route_reply_launches(void) { return g_reply_launches.load(std::memory_order_relaxed); }
+
 // The new-connection step of qpp_session_accept_unprotect.
 struct AcceptArgs {
     qpp_keytab *kt;
@@ -510,18 +618,32 @@ struct AcceptArgs {
     uint8_t *secrets_out;
 };
 
+// The answering step of qpp_session_accept_reply_unprotect, beside AcceptArgs.
+struct ReplyArgs {
+    const qpp_keytab *reply_kt;
+    const uint8_t *addr, *rnd;
+    uint64_t token_ctr;
+    const uint32_t *versions;
+    uint32_t n_versions, reply_flags;
+    uint8_t *reply_out;
+    qpp_reply_rec *reply_rec_out;
+};
+
 // The session forms.  walk_form: conn_slot / conn_expected are the walk's
 // per-key-set and per-space arrays, and the routing kernel's per-connection
 // ones (the 1-RTT slot, the application space's number) are taken from them.
 // ac (walk form only; NULL or no candidates: nothing of it happens): the
 // accepting kernel and the key derivation between the walk and the unprotect.
+// rp (with ac's candidates only; NULL or no flag: nothing of it happens): the
+// assembling kernel after the accepting one, the two reply protects after the
+// batch's unprotect.
 static int route_unprotect(qpp_session *s, const qpp_keytab *kt, const qpp_cidmap *m, uint32_t cid_len,
                            const uint64_t *off, const uint32_t *len, uint32_t n, const uint8_t *in, size_t in_len,
                            bool walk_form, const uint32_t *long_idx, uint32_t n_long, const uint32_t *conn_slot,
                            const uint64_t *conn_expected, uint32_t n_conn, uint16_t desc_flags, uint8_t *out,
                            size_t out_len, qpp_desc *desc_out, qpp_route_rec *route_out, qpp_result *res,
                            qpp_walk_rec *walk_out, uint32_t *walk_n_out, const AcceptArgs *ac = NULL,
-                           const uint32_t *conn_next = NULL, uint8_t *phase_out = NULL)
+                           const uint32_t *conn_next = NULL, uint8_t *phase_out = NULL, const ReplyArgs *rp = NULL)
 {
     if (!s || !kt || !m || cid_len < 1 || cid_len > QPP_CID_MAX) return QPP_E_ARG;
     const uint32_t n_acc = ac ? ac->n : 0;
@@ -569,6 +691,21 @@ static int route_unprotect(qpp_session *s, const qpp_keytab *kt, const qpp_cidma
             return QPP_E_NOMEM;
         }
     }
+    const bool replies = rp && n_acc && rp->reply_flags;
+    if (replies) {
+        const bool retry = rp->reply_flags & QPP_RP_RETRY;
+        if ((rp->reply_flags & ~(QPP_RP_VN | QPP_RP_RETRY)) || !rp->reply_kt || !rp->rnd || !rp->reply_out ||
+            !rp->reply_rec_out || qpp_keytab_capacity(rp->reply_kt) < 3 || !rp->versions || rp->n_versions < 1 ||
+            rp->n_versions > QPP_RP_MAX_VERSIONS)
+            return QPP_E_ARG;
+        if (retry) {
+            if (!rp->addr || rp->token_ctr + n_acc < rp->token_ctr) return QPP_E_ARG;
+            for (uint32_t a = 0; a < n_acc; ++a) {
+                const uint8_t al = rp->addr[(size_t)a * QPP_RP_ADDR_STRIDE];
+                if (al != 6 && al != 18) return QPP_E_ARG;
+            }
+        }
+    }
     const uint32_t nd = n + 3u * n_long;  // descriptors and results
     // scratch: [off | len | conn_slot | conn_expected | long_idx | key-set slots | space numbers]
     // go up in one copy, [desc | route | results | walk records | walk counts] come back in one
@@ -579,7 +716,9 @@ static int route_unprotect(qpp_session *s, const qpp_keytab *kt, const qpp_cidma
                  o_arow = o_kexp + (n_long ? al256((size_t)n_conn * QPP_SPACES * 8) : 0),
                  o_aslot = o_arow + (n_acc ? al256((size_t)n_acc * 4) : 0),
                  o_next = o_aslot + (n_acc ? al256((size_t)n_acc * 8) : 0),
-                 up = o_next + (any_next ? al256((size_t)n_conn * 4) : 0);
+                 o_addr = o_next + (any_next ? al256((size_t)n_conn * 4) : 0),
+                 o_rand = o_addr + (replies ? al256((size_t)n_acc * QPP_RP_ADDR_STRIDE) : 0),
+                 up = o_rand + (replies ? al256((size_t)n_acc * QPP_RP_RAND_STRIDE) : 0);
     const size_t o_route = al256((size_t)nd * sizeof(qpp_desc)),
                  o_res = o_route + al256((size_t)n * sizeof(qpp_route_rec)),
                  o_walk = o_res + al256((size_t)nd * sizeof(qpp_result)),
@@ -588,12 +727,17 @@ static int route_unprotect(qpp_session *s, const qpp_keytab *kt, const qpp_cidma
                  o_km = o_acc + (n_acc ? al256((size_t)n_acc * sizeof(qpp_accept_rec)) : 0),
                  o_sec = o_km + (n_acc ? al256((size_t)n_acc * 2 * sizeof(qpp_key_material)) : 0),
                  o_phase = o_sec + (n_acc ? al256((size_t)n_acc * 64) : 0),
-                 down = o_phase + (any_next ? al256((size_t)n) : 0);
-    // the candidates' qpp_initial records never leave the device: scratch past both copies
+                 o_reply = o_phase + (any_next ? al256((size_t)n) : 0),
+                 o_rrec = o_reply + (replies ? (size_t)n_acc * QPP_REPLY_STRIDE : 0),
+                 o_rres = o_rrec + (replies ? al256((size_t)n_acc * sizeof(qpp_reply_rec)) : 0),
+                 down = o_rres + (replies ? al256((size_t)n_acc * 2 * sizeof(qpp_result)) : 0);
+    // the candidates' qpp_initial records and the reply descriptors (the seals,
+    // then the tags) never leave the device: scratch past both copies
     const size_t ini_bytes = n_acc ? al256((size_t)n_acc * sizeof(qpp_initial)) : 0;
+    const size_t rdesc_bytes = replies ? al256((size_t)n_acc * 2 * sizeof(qpp_desc)) : 0;
     qpp_session_bufs b;
     const size_t need = in_len > out_len ? in_len : out_len;
-    int rc = qpp_internal_session_bufs(s, need, nd, up + down + ini_bytes, &b);
+    int rc = qpp_internal_session_bufs(s, need, nd, up + down + ini_bytes + rdesc_bytes, &b);
     if (rc != QPP_OK) return rc;
     uint8_t *hu = b.h_scratch, *du = b.d_scratch, *hd = b.h_scratch + up, *dd = b.d_scratch + up;
     memcpy(hu, off, (size_t)n * 8);
@@ -621,6 +765,11 @@ static int route_unprotect(qpp_session *s, const qpp_keytab *kt, const qpp_cidma
         memcpy(hu + o_aslot, ac->slot, (size_t)n_acc * 8);
     }
     if (any_next) memcpy(hu + o_next, conn_next, (size_t)n_conn * 4);
+    if (replies) {
+        if (rp->addr) memcpy(hu + o_addr, rp->addr, (size_t)n_acc * QPP_RP_ADDR_STRIDE);
+        else memset(hu + o_addr, 0, (size_t)n_acc * QPP_RP_ADDR_STRIDE);
+        memcpy(hu + o_rand, rp->rnd, (size_t)n_acc * QPP_RP_RAND_STRIDE);
+    }
     if (in_len && in != b.h_in) memcpy(b.h_in, in, in_len);  // staged by the caller already?
     HIPCHK(hipMemcpyAsync(du, hu, up, hipMemcpyHostToDevice, b.stream));
     if (in_len) HIPCHK(hipMemcpyAsync(b.d_in, b.h_in, in_len, hipMemcpyHostToDevice, b.stream));
@@ -648,6 +797,16 @@ static int route_unprotect(qpp_session *s, const qpp_keytab *kt, const qpp_cidma
                               (const uint32_t *)(du + o_aslot), n_acc, ac->flags, desc_flags, d_ini, d_desc,
                               (qpp_accept_rec *)(dd + o_acc), b.stream);
         if (rc != QPP_OK) return rc;
+        if (replies) {
+            qpp_desc *d_seal = (qpp_desc *)(dd + down + ini_bytes);
+            rc = qpp_route_reply((const uint64_t *)du, (const uint32_t *)(du + o_len), n, b.d_in,
+                                 (const uint32_t *)(du + o_long), n_long, (const qpp_walk_rec *)(dd + o_walk),
+                                 (const uint32_t *)(du + o_arow), (const qpp_accept_rec *)(dd + o_acc), n_acc,
+                                 du + o_addr, du + o_rand, rp->token_ctr, rp->versions, rp->n_versions,
+                                 rp->reply_flags, dd + o_reply, d_seal, d_seal + n_acc,
+                                 (qpp_reply_rec *)(dd + o_rrec), b.stream);
+            if (rc != QPP_OK) return rc;
+        }
         // notes every candidate's slots in the table's bookkeeping before the
         // unprotect launch below chooses its kernel form from it
         rc = qpp_keytab_derive_initial_device(ac->kt, d_ini, n_acc, ac->slot, (qpp_key_material *)(dd + o_km),
@@ -662,6 +821,15 @@ static int route_unprotect(qpp_session *s, const qpp_keytab *kt, const qpp_cidma
     }
     rc = qpp_unprotect(kt, d_desc, nd, b.d_in, b.d_out, d_res, b.stream);
     if (rc != QPP_OK) return rc;
+    if (replies) {
+        // in place in the reply buffer: every token sealed, then every Retry integrity tag
+        const qpp_desc *d_seal = (const qpp_desc *)(dd + down + ini_bytes);
+        qpp_result *d_rres = (qpp_result *)(dd + o_rres);
+        rc = qpp_protect(rp->reply_kt, d_seal, n_acc, dd + o_reply, dd + o_reply, d_rres, b.stream);
+        if (rc != QPP_OK) return rc;
+        rc = qpp_protect(rp->reply_kt, d_seal + n_acc, n_acc, dd + o_reply, dd + o_reply, d_rres + n_acc, b.stream);
+        if (rc != QPP_OK) return rc;
+    }
     if (out_len) HIPCHK(hipMemcpyAsync(b.h_out, b.d_out, out_len, hipMemcpyDeviceToHost, b.stream));
     HIPCHK(hipMemcpyAsync(hd, dd, down, hipMemcpyDeviceToHost, b.stream));
     HIPCHK(hipStreamSynchronize(b.stream));
@@ -679,6 +847,21 @@ static int route_unprotect(qpp_session *s, const qpp_keytab *kt, const qpp_cidma
         memcpy(ac->acc_out, hd + o_acc, (size_t)n_acc * sizeof(qpp_accept_rec));
         memcpy(ac->km_out, hd + o_km, (size_t)n_acc * 2 * sizeof(qpp_key_material));
         memcpy(ac->secrets_out, hd + o_sec, (size_t)n_acc * 64);
+    }
+    if (replies) {
+        memcpy(rp->reply_out, hd + o_reply, (size_t)n_acc * QPP_REPLY_STRIDE);
+        memcpy(rp->reply_rec_out, hd + o_rrec, (size_t)n_acc * sizeof(qpp_reply_rec));
+        // a Retry is whole or it is not sent
+        const qpp_result *rres = (const qpp_result *)(hd + o_rres);
+        for (uint32_t a = 0; a < n_acc; ++a) {
+            qpp_reply_rec &q = rp->reply_rec_out[a];
+            if (q.kind != QPP_RP_KIND_RETRY) continue;
+            const uint16_t st = rres[a].status != QPP_S_OK ? rres[a].status : rres[n_acc + a].status;
+            if (st == QPP_S_OK) continue;
+            q.len = 0;
+            q.kind = QPP_RP_KIND_NONE;
+            q.status = (uint8_t)st;
+        }
     }
     return QPP_OK;
 }
@@ -744,6 +927,26 @@ int qpp_session_accept_unprotect(qpp_session *s, qpp_keytab *kt, const qpp_cidma
     return settle(s, route_unprotect(s, kt, m, cid_len, off, len, n, in, in_len, true, long_idx, n_long, conn_slot,
                                      conn_expected, n_conn, desc_flags, out, out_len, desc_out, route_out, res,
                                      walk_out, walk_n_out, &ac));
+}
+
+int qpp_session_accept_reply_unprotect(qpp_session *s, qpp_keytab *kt, const qpp_cidmap *m, uint32_t cid_len,
+                                       const uint64_t *off, const uint32_t *len, uint32_t n, const uint8_t *in,
+                                       size_t in_len, const uint32_t *long_idx, uint32_t n_long,
+                                       const uint32_t *conn_slot, const uint64_t *conn_expected, uint32_t n_conn,
+                                       uint16_t desc_flags, const uint32_t *acc_row, const uint32_t *acc_slot,
+                                       uint32_t n_acc, uint32_t accept_flags, const qpp_keytab *reply_kt,
+                                       const uint8_t *addr, const uint8_t *rnd, uint64_t token_ctr,
+                                       const uint32_t *versions, uint32_t n_versions, uint32_t reply_flags,
+                                       uint8_t *out, size_t out_len, qpp_desc *desc_out, qpp_route_rec *route_out,
+                                       qpp_result *res, qpp_walk_rec *walk_out, uint32_t *walk_n_out,
+                                       qpp_accept_rec *acc_out, qpp_key_material *km_out, uint8_t *secrets_out,
+                                       uint8_t *reply_out, qpp_reply_rec *reply_rec_out)
+{
+    const AcceptArgs ac = {kt, acc_row, acc_slot, n_acc, accept_flags, acc_out, km_out, secrets_out};
+    const ReplyArgs rp = {reply_kt, addr, rnd, token_ctr, versions, n_versions, reply_flags, reply_out, reply_rec_out};
+    return settle(s, route_unprotect(s, kt, m, cid_len, off, len, n, in, in_len, true, long_idx, n_long, conn_slot,
+                                     conn_expected, n_conn, desc_flags, out, out_len, desc_out, route_out, res,
+                                     walk_out, walk_n_out, &ac, NULL, NULL, &rp));
 }
 
 }  // extern "C"

@@ -104,6 +104,19 @@ A_NEED_TOKEN = 1  # QPP_A_NEED_TOKEN: the server's Retry mode, an Initial must c
 PHASE = np.dtype("u1")
 PHASE_CURRENT, PHASE_NEXT = 0, 1
 NEXT_SLOT = np.dtype("<u4")
+# qpp_reply_rec: what qpp_route_reply built for one candidate: where the packet
+# to send lies in the reply buffer (REPLY_STRIDE bytes per candidate), its
+# length, an RP_KIND_* and an RP_* status (or the S_* of a failed seal / tag)
+REPLY = np.dtype([("off", "<u4"), ("len", "<u2"), ("kind", "u1"), ("status", "u1")])
+REPLY_STRIDE = 256          # QPP_REPLY_STRIDE
+RP_MAX_VERSIONS = 16        # QPP_RP_MAX_VERSIONS
+RP_ADDR_STRIDE, RP_RAND_STRIDE = 20, 16
+RP_VN, RP_RETRY = 1, 2      # reply_flags
+RP_KIND_NONE, RP_KIND_VN, RP_KIND_RETRY = 0, 1, 2
+RP_OK, RP_BOUNDS, RP_ADDR = 0, 0x40, 0x41
+# the reply key table's slots: the Retry keys of versions 1 and 2, the server's token key
+RP_SLOT_V1, RP_SLOT_V2, RP_SLOT_TOKEN = 0, 1, 2
+assert REPLY.itemsize == 8
 assert DESC.itemsize == 40 and RESULT.itemsize == 16 and KEY_MATERIAL.itemsize == 84
 assert WALK.itemsize == 24 and ACCEPT.itemsize == 8
 assert SECRET.itemsize == 80 and INITIAL.itemsize == 32

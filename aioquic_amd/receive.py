@@ -34,6 +34,7 @@ per datagram, where the reference logs nothing).
 
 from __future__ import annotations
 
+import os
 from dataclasses import dataclass, field
 from typing import Any, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
@@ -797,9 +798,53 @@ def accept_routed(router, datagrams: Sequence[bytes], accept, *, need_token: boo
     the device leaves to the host walk, and so on) goes through
     receive_routed, and nothing is accepted.  ValueError for a router that
     holds a client connection checking its host CIDs."""
+    return _accept_routed(router, datagrams, accept, need_token, None)[:3]
+
+
+def answer_routed(router, datagrams: Sequence[bytes], addrs: Sequence[Any], accept, *, tokens=None,
+                  supported_versions: Sequence[int] = (1, 0x6B3343CF)):
+    """accept_routed for a server that also answers what it does not accept.
+
+    Returns (records, unrouted, accepted, replies).  The two verdicts after
+    which the reference's server sends a packet and drops the datagram
+    (asyncio/server.py:71-111) no longer come back in `unrouted` to be
+    answered one AEAD call at a time: in the same fused call
+    (_crypto.receive_accept_reply) a kernel assembles a Version Negotiation
+    packet for every candidate Initial of a version that is neither 1 nor 2
+    (encode_quic_version_negotiation, quic/packet.py:317-334, advertising
+    `supported_versions`) and, in Retry mode, a Retry for every Initial
+    without a token (encode_quic_retry, quic/packet.py:288-314), and two
+    launches over all of them seal the tokens and append the Retry integrity
+    tags.  `replies` is [(datagram_index, packet)] in datagram order, each to
+    be sent to addrs[datagram_index]; a replied datagram leaves `unrouted`,
+    as server.py returns after its sendto.
+
+    `tokens` is a retry.RetryTokens, or None for a server not in Retry mode:
+    then no token is demanded (accept_routed's need_token=False) and only
+    Version Negotiation replies are built.  With it, an Initial that carries
+    a token is accepted on the device as by accept_routed(need_token=True);
+    validating the token (tokens.validate_token(addrs[i], header.token)) is
+    `accept`'s, as server.py:112-120 does it before it creates a connection.
+    A Retry's source CID is 8 random bytes (server.py:98) and its token is
+    what tokens.seal gives for the counter it carries; the counters of one
+    call are consecutive, taken with tokens.take.
+
+    Everything else is accept_routed's: the candidates are cut to the key
+    slots left (two each, whether they end accepted or answered), and a batch
+    that accept_routed hands to receive_routed comes back from there with
+    nothing accepted and no replies."""
+    return _accept_routed(router, datagrams, accept, tokens is not None, (addrs, tokens, supported_versions))
+
+
+_vn_only = None  # the 3-slot reply table of servers not in Retry mode (its token slot is never used)
+
+
+def _accept_routed(router, datagrams, accept, need_token: bool, answer):
+    """accept_routed (answer None) and answer_routed (answer = (addrs, tokens,
+    supported_versions)): (records, unrouted, accepted, replies)."""
     datagrams = datagrams if isinstance(datagrams, list) else list(datagrams)
     if not datagrams:
-        return [], [], []
+        return [], [], [], []
     conns = router.conns
     if any(c is not None and c.is_client and c.host_cids is not None for c in conns):
         raise ValueError("accept_routed is a server's: the router holds a client connection")
@@ -817,14 +862,30 @@ def accept_routed(router, datagrams: Sequence[bytes], accept, *, need_token: boo
         keep = min(len(cand), slots.room() // 2)
         rows, cand = rows[:keep], cand[:keep]
     if not cand:
-        return receive_routed(router, datagrams) + ([],)
+        return receive_routed(router, datagrams) + ([], [])
+    sent = None
+    if answer is not None:
+        from .retry import RetryTokens, packed_address
+
+        global _vn_only
+        addrs, tokens, versions = answer
+        if tokens is None and _vn_only is None:
+            _vn_only = RetryTokens()
+        reply_args = ((tokens or _vn_only).table,
+                      b"".join(packed_address(addrs[i]) for i in cand) if tokens is not None else b"",
+                      os.urandom(L.RP_RAND_STRIDE * len(cand)), tokens.take(len(cand)) if tokens is not None else 0,
+                      np.asarray(list(versions), np.uint32).tobytes(),
+                      L.RP_VN | (L.RP_RETRY if tokens is not None else 0))
     taken = slots.reserve(2 * len(cand))  # inside room(): no refill
     try:
-        route_b, _, longs, found = _crypto.receive_accept(
-            slots.table, router.map, cid_len, datagrams, *arrays, ReceivedPacket, QuicPacketType.ONE_RTT,
-            Epoch.ONE_RTT, bytes(bool(c is not None and c.closed) for c in conns), 1,
-            np.asarray(rows, np.uint32).tobytes(), np.asarray(taken, np.uint32).tobytes(),
-            L.A_NEED_TOKEN if need_token else 0)
+        call_args = (slots.table, router.map, cid_len, datagrams, *arrays, ReceivedPacket, QuicPacketType.ONE_RTT,
+                     Epoch.ONE_RTT, bytes(bool(c is not None and c.closed) for c in conns), 1,
+                     np.asarray(rows, np.uint32).tobytes(), np.asarray(taken, np.uint32).tobytes(),
+                     L.A_NEED_TOKEN if need_token else 0)
+        if answer is None:
+            route_b, _, longs, found = _crypto.receive_accept(*call_args)
+        else:
+            route_b, _, longs, found, sent = _crypto.receive_accept_reply(*call_args, *reply_args)
         route = np.frombuffer(route_b, dtype=L.ROUTE)
         cls, rconn = route["cls"], route["conn"]
         walk = np.frombuffer(longs[1], dtype=L.WALK).reshape(-1, L.WALK_MAX)
@@ -862,7 +923,13 @@ def accept_routed(router, datagrams: Sequence[bytes], accept, *, need_token: boo
     finally:
         slots.give_back(taken)
     if host:
-        return receive_routed(router, datagrams) + ([],)
+        return receive_routed(router, datagrams) + ([], [])
+    replies = []
+    if sent is not None:
+        rrec = np.frombuffer(sent[1], dtype=L.REPLY)
+        for a in np.flatnonzero(rrec["kind"] != L.RP_KIND_NONE).tolist():
+            at = int(rrec["off"][a])
+            replies.append((cand[a], sent[0][at:at + int(rrec["len"][a])]))
     others = [(c.cryptos_initial[v], h.destination_cid, v) for _, c, _, h in new for v in c.supported_versions
               if v != h.version and v in c.cryptos_initial and c.cryptos_initial[v].recv.aead is None]
     if others:
@@ -872,8 +939,10 @@ def accept_routed(router, datagrams: Sequence[bytes], accept, *, need_token: boo
     routed = ((cls == L.R_SHORT) | (cls == L.R_LONG)) & (rconn != L.CONN_NONE)
     here = routed.copy()
     here[np.asarray(list(joined), np.int64)] = True
-    unrouted = [(int(i), int(cls[i])) for i in np.flatnonzero(~here)]
+    gone = here.copy()
+    gone[np.asarray([i for i, _ in replies], np.int64)] = True  # answered: server.py returns after sendto
+    unrouted = [(int(i), int(cls[i])) for i in np.flatnonzero(~gone)]
     recs = _routed_long(router.conns, datagrams, cid_len, np.flatnonzero(here).tolist(), cls, rconn, longs, slots,
                         joined)
     assert recs is not None  # _host_walk_needed ruled its reasons out
-    return recs, unrouted, [(i, c) for i, c, _, _ in new]
+    return recs, unrouted, [(i, c) for i, c, _, _ in new], replies

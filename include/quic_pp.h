@@ -537,6 +537,89 @@ int qpp_route_accept(const uint64_t *d_off, const uint32_t *d_len, uint32_t n, c
  * library loaded).  Diagnostic: a batch without candidates makes none. */
 uint64_t qpp_route_accept_launches(void);
 
+/* qpp_route_reply: the packets a server sends instead of accepting, for the
+ * two verdicts of qpp_route_accept after which the reference's server sends
+ * something and drops the datagram (asyncio/server.py:71-111): a Version
+ * Negotiation packet for QPP_ACC_VERSION (encode_quic_version_negotiation,
+ * quic/packet.py:317-334) and, in Retry mode, a Retry for QPP_ACC_NO_TOKEN
+ * (encode_quic_retry, quic/packet.py:288-314, around a token whose plaintext
+ * is the buffer of QuicRetryTokenHandler.create_token, quic/retry.py:25-28).
+ * Asynchronous on `stream`; runs after qpp_route_accept on the same stream,
+ * over the same datagram arrays, d_long_idx, d_walk, d_acc_row and the d_acc
+ * that call wrote (all read only here).  One lane per candidate; no cipher
+ * runs here.  Candidate a owns the QPP_REPLY_STRIDE bytes at a * 256 of
+ * d_reply (256-byte aligned memory), d_seal[a], d_tag[a] and d_rec[a]; all are
+ * written whole for every candidate, the region zero filled first, so the same
+ * input gives the same bytes.
+ * With dl / sl the DCID / SCID lengths of packet 0's walk record, a lane that
+ * owes a reply first checks dl <= 20, sl <= 20 and 7 + dl + sl <= d_len[i]
+ * against d_len, then that bytes 5 and 6 + dl of the datagram are dl and sl;
+ * a failure gives {kind none, QPP_RP_BOUNDS}.  It reads the datagram's bytes
+ * [5, 7 + dl + sl) and nothing else of it.
+ *   QPP_ACC_VERSION with QPP_RP_VN in reply_flags: the region holds [0x80 |
+ *   (d_rand[16a + 8] & 0x7f), four zero bytes, sl, the client's SCID, dl, its
+ *   DCID (dl may be 0), versions[0 .. n_versions) big-endian]; d_rec[a] =
+ *   {256a, 7 + sl + dl + 4 n_versions, QPP_RP_KIND_VN, QPP_RP_OK}.
+ *   QPP_ACC_NO_TOKEN with QPP_RP_RETRY: the region holds the pseudo-packet of
+ *   RFC 9001 sec. 5.8 from offset 0: [dl, the client's DCID], then at pkt = 1 +
+ *   dl the Retry packet [0xF0 (version 1) or 0xC0 (version 2), the version,
+ *   sl, the client's SCID, 8, d_rand[16a .. 16a + 8) as the new source CID],
+ *   then at tok = pkt + 7 + sl + 8 the token: ctr = token_ctr + a as 8
+ *   big-endian bytes, the plaintext P = [alen, address, dl, DCID, 8, the new
+ *   source CID] with alen = d_addr[20a] (6 or 18, else {none, QPP_RP_ADDR})
+ *   and the address the alen bytes after it (the packed IP, then the port
+ *   big-endian: encode_address), and 16 zero bytes for the seal's tag; T = 8 +
+ *   |P| + 16.  d_seal[a] = {in_off = out_off = 256a + tok, len = |P|, hdr_len
+ *   = 8, QPP_F_NO_HP, pn = ctr, slot 2}; d_tag[a] = {in_off = out_off = 256a,
+ *   len = 0, hdr_len = tok + T, QPP_F_NO_HP, pn = 0, slot 0 for version 1 and
+ *   1 for version 2}; d_rec[a] = {256a + pkt, 7 + sl + 8 + T + 16,
+ *   QPP_RP_KIND_RETRY, QPP_RP_OK}.  tok + T <= 129, and the integrity tag ends
+ *   at 145 at the most.
+ *   Anything else: d_rec[a] = {256a, 0, QPP_RP_KIND_NONE, status}.
+ * Every candidate without a Retry gets two inert descriptors, as qpp_route
+ * writes them: len 0, QPP_SLOT_NONE, both offsets 256a.
+ * The caller then runs qpp_protect(reply_kt, d_seal, n_acc, d_reply, d_reply,
+ * ...) and, after it on the same stream, the same over d_tag: the first seals
+ * every token in place, the second appends every Retry integrity tag
+ * (get_retry_integrity_tag, quic/packet.py:135-159).  reply_kt is a key table
+ * of its own by this convention, which nothing enforces: slot 0 the Retry key
+ * and nonce of RFC 9001 sec. 5.8, slot 1 those of RFC 9369 sec. 3.3.3, slot 2
+ * the server's own token key and IV, all QPP_AES_128_GCM.  No (key, nonce)
+ * pair of slot 2 may repeat: the caller never hands out a counter twice.
+ * versions[n_versions] is host memory, read before the call returns.
+ * QPP_E_ARG: a NULL array with n_acc > 0 (d_addr may be NULL without
+ * QPP_RP_RETRY), a reply_flags bit other than QPP_RP_VN | QPP_RP_RETRY,
+ * n_versions outside 1..QPP_RP_MAX_VERSIONS, or NULL versions.  n_acc == 0
+ * returns QPP_OK and launches nothing. */
+#define QPP_REPLY_STRIDE 256
+#define QPP_RP_MAX_VERSIONS 16
+#define QPP_RP_ADDR_STRIDE 20
+#define QPP_RP_RAND_STRIDE 16
+#define QPP_RP_VN 1u
+#define QPP_RP_RETRY 2u
+#define QPP_RP_KIND_NONE 0
+#define QPP_RP_KIND_VN 1
+#define QPP_RP_KIND_RETRY 2
+#define QPP_RP_OK 0
+#define QPP_RP_BOUNDS 0x40  /* the walk record's CID lengths do not fit the datagram */
+#define QPP_RP_ADDR 0x41    /* an address length that is neither 6 nor 18 */
+typedef struct qpp_reply_rec {
+    uint32_t off;        /* of the packet to send, in the reply buffer */
+    uint16_t len;        /* its length, or 0 */
+    uint8_t kind;        /* QPP_RP_KIND_* */
+    uint8_t status;      /* QPP_RP_OK, QPP_RP_BOUNDS, QPP_RP_ADDR; from the session form also the
+                            QPP_S_* of a Retry's failed seal or tag, its kind then QPP_RP_KIND_NONE */
+} qpp_reply_rec;         /* 8 bytes */
+int qpp_route_reply(const uint64_t *d_off, const uint32_t *d_len, uint32_t n, const uint8_t *d_in,
+                    const uint32_t *d_long_idx, uint32_t n_long, const qpp_walk_rec *d_walk,
+                    const uint32_t *d_acc_row, const qpp_accept_rec *d_acc, uint32_t n_acc, const uint8_t *d_addr,
+                    const uint8_t *d_rand, uint64_t token_ctr, const uint32_t *versions, uint32_t n_versions,
+                    uint32_t reply_flags, uint8_t *d_reply, qpp_desc *d_seal, qpp_desc *d_tag, qpp_reply_rec *d_rec,
+                    void *stream);
+/* qpp_route_reply launches of the assembling kernel (process-wide, since the
+ * library loaded).  Diagnostic: a call without candidates makes none. */
+uint64_t qpp_route_reply_launches(void);
+
 /* qpp_route_phase: a peer's key update (quic/crypto.py:91-96, :184-192)
  * resolved on the device ahead of the unprotect.  Asynchronous on `stream`;
  * runs after qpp_route (and qpp_route_walk) on the same stream, over the
@@ -690,6 +773,43 @@ int qpp_session_accept_unprotect(qpp_session *s, qpp_keytab *kt, const qpp_cidma
                                  qpp_desc *desc_out, qpp_route_rec *route_out, qpp_result *res,
                                  qpp_walk_rec *walk_out, uint32_t *walk_n_out, qpp_accept_rec *acc_out,
                                  qpp_key_material *km_out, uint8_t *secrets_out);
+/* qpp_session_accept_unprotect for a server that also answers what it does
+ * not accept (asyncio/server.py:71-111; quic/packet.py:288-334; quic/retry.py):
+ * qpp_route_reply runs after the accepting kernel, and after the batch's
+ * unprotect two qpp_protect launches over the n_acc reply regions seal the
+ * tokens and append the Retry integrity tags, both with reply_kt (the slot
+ * convention of qpp_route_reply; capacity >= 3).  addr[20 n_acc] (may be NULL
+ * without QPP_RP_RETRY), rnd[16 n_acc], token_ctr, versions[n_versions] and
+ * reply_flags are qpp_route_reply's inputs, in host memory here.  The inputs
+ * ride up in the existing scratch copy; the reply buffer, the records and the
+ * two launches' results ride down in the existing one; the descriptors never
+ * leave the device.  reply_out[256 n_acc] receives the reply buffer and
+ * reply_rec_out[n_acc] the records: the packet to send for candidate a is
+ * reply_out[rec.off .. rec.off + rec.len) when rec.kind is not
+ * QPP_RP_KIND_NONE.  A Retry whose seal or tag result is not QPP_S_OK is
+ * downgraded on the host to {len 0, QPP_RP_KIND_NONE, that status}: a reply
+ * is never half built.
+ * Checked on the host before anything is launched or noted, besides what the
+ * accept form checks: with reply_flags != 0, reply_kt, rnd, reply_out and
+ * reply_rec_out given, qpp_keytab_capacity(reply_kt) >= 3, no reply_flags bit
+ * other than QPP_RP_VN | QPP_RP_RETRY, 1 <= n_versions <= QPP_RP_MAX_VERSIONS
+ * with versions given, and with QPP_RP_RETRY addr given, every addr[20a] 6 or
+ * 18 and token_ctr + n_acc not wrapping.  A violation is QPP_E_ARG and nothing
+ * is touched.  With reply_flags == 0 (or n_acc == 0) the call is
+ * qpp_session_accept_unprotect: the same launches, the same bytes, and the
+ * reply arguments are not looked at. */
+int qpp_session_accept_reply_unprotect(qpp_session *s, qpp_keytab *kt, const qpp_cidmap *m, uint32_t cid_len,
+                                       const uint64_t *off, const uint32_t *len, uint32_t n, const uint8_t *in,
+                                       size_t in_len, const uint32_t *long_idx, uint32_t n_long,
+                                       const uint32_t *conn_slot, const uint64_t *conn_expected, uint32_t n_conn,
+                                       uint16_t desc_flags, const uint32_t *acc_row, const uint32_t *acc_slot,
+                                       uint32_t n_acc, uint32_t accept_flags, const qpp_keytab *reply_kt,
+                                       const uint8_t *addr, const uint8_t *rnd, uint64_t token_ctr,
+                                       const uint32_t *versions, uint32_t n_versions, uint32_t reply_flags,
+                                       uint8_t *out, size_t out_len, qpp_desc *desc_out, qpp_route_rec *route_out,
+                                       qpp_result *res, qpp_walk_rec *walk_out, uint32_t *walk_n_out,
+                                       qpp_accept_rec *acc_out, qpp_key_material *km_out, uint8_t *secrets_out,
+                                       uint8_t *reply_out, qpp_reply_rec *reply_rec_out);
 /* The session's own pinned staging buffers, sized for at least `bytes` of
  * input and of output and n packets; valid until the next call on the
  * session.  A caller that assembles its input straight into *h_in and passes
