@@ -83,6 +83,10 @@ def load() -> ctypes.CDLL:
         c.c_size_t, c.c_uint64, c.c_void_p, c.POINTER(c.c_size_t), c.POINTER(c.c_uint64),
     ]
     lib.qo_hp_mask.argtypes = [c.c_int, c.c_char_p, c.c_char_p, c.c_void_p]
+    lib.qo_chacha20_block.argtypes = [c.c_char_p, c.c_uint32, c.c_char_p, c.c_void_p]
+    lib.qo_chacha20_block.restype = None
+    lib.qo_poly1305.argtypes = [c.c_char_p, c.c_char_p, c.c_size_t, c.c_void_p]
+    lib.qo_poly1305.restype = None
     for f in ("qo_protect_batch", "qo_unprotect_batch"):
         getattr(lib, f).argtypes = [c.c_void_p, c.c_uint32, c.c_void_p, c.c_uint32,
                                     c.c_void_p, c.c_void_p, c.c_void_p]
@@ -193,6 +197,19 @@ def aead_decrypt(suite, key, iv, data: bytes, aad: bytes, pn: int) -> bytes:
 def hp_mask(suite, hp, sample: bytes) -> bytes:
     out = ctypes.create_string_buffer(16)
     lib().qo_hp_mask(suite, hp, sample, out)
+    return out.raw
+
+
+def chacha20_block(key: bytes, counter: int, nonce: bytes) -> bytes:
+    out = ctypes.create_string_buffer(64)
+    lib().qo_chacha20_block(key, counter, nonce, out)
+    return out.raw
+
+
+def poly1305(key: bytes, msg: bytes) -> bytes:
+    """RFC 8439 sec. 2.5 under the 32-byte one-time key r || s."""
+    out = ctypes.create_string_buffer(16)
+    lib().qo_poly1305(key, msg, len(msg), out)
     return out.raw
 
 

@@ -248,13 +248,13 @@ static void poly_init(poly_t *p, const uint8_t k[32])
     p->h0 = p->h1 = p->h2 = 0;
 }
 
-/* h = (h + m + 2^128) * r mod 2^130-5 for one full 16-byte block */
-static void poly_block(poly_t *p, const uint8_t m[16])
+/* h = (h + m + hibit 2^128) * r mod 2^130-5 for one 16-byte block */
+static void poly_block_hi(poly_t *p, const uint8_t m[16], uint64_t hibit)
 {
     typedef unsigned __int128 u128;
     u128 t0 = (u128)p->h0 + rd64le(m);
     u128 t1 = (u128)p->h1 + rd64le(m + 8) + (uint64_t)(t0 >> 64);
-    uint64_t h0 = (uint64_t)t0, h1 = (uint64_t)t1, h2 = p->h2 + (uint64_t)(t1 >> 64) + 1;
+    uint64_t h0 = (uint64_t)t0, h1 = (uint64_t)t1, h2 = p->h2 + (uint64_t)(t1 >> 64) + hibit;
     uint64_t r0 = p->r0, r1 = p->r1, sr1 = r1 + (r1 >> 2); /* 5*r1/4, exact since r1%4==0 */
     /* h*r mod p with 2^130 == 5 folded into r1's contribution */
     u128 d0 = (u128)h0 * r0 + (u128)h1 * sr1;
@@ -274,6 +274,9 @@ static void poly_block(poly_t *p, const uint8_t m[16])
     h2 += (uint64_t)(t >> 64);
     p->h0 = h0; p->h1 = h1; p->h2 = h2;
 }
+
+/* one full block (every AEAD block is: RFC 8439 sec. 2.8) */
+static void poly_block(poly_t *p, const uint8_t m[16]) { poly_block_hi(p, m, 1); }
 
 static void poly_finish(poly_t *p, uint8_t tag[16])
 {
@@ -306,6 +309,23 @@ static void poly_padded(poly_t *p, const uint8_t *d, size_t n)
         d += k;
         n -= k;
     }
+}
+
+/* Poly1305 alone (RFC 8439 sec. 2.5.1) under a 32-byte one-time key: a final
+ * partial block takes a 0x01 byte and zeros instead of the 2^128 bit.  For
+ * the tests of the MAC's carry edges (tests/test_p130_host.py). */
+void qo_poly1305(const uint8_t key[32], const uint8_t *msg, size_t len, uint8_t tag[16])
+{
+    poly_t p;
+    poly_init(&p, key);
+    for (; len >= 16; msg += 16, len -= 16) poly_block(&p, msg);
+    if (len) {
+        uint8_t blk[16] = {0};
+        memcpy(blk, msg, len);
+        blk[len] = 1;
+        poly_block_hi(&p, blk, 0);
+    }
+    poly_finish(&p, tag);
 }
 
 /* RFC 8439 sec. 2.8 */

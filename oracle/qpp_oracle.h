@@ -21,6 +21,7 @@ int qo_aes_expand(const uint8_t *key, int key_len, uint32_t *rk);
 void qo_aes_block(const uint32_t *rk, int nr, const uint8_t in[16], uint8_t out[16]);
 void qo_chacha20_block(const uint8_t key[32], uint32_t counter, const uint8_t nonce[12],
                        uint8_t out[64]);
+void qo_poly1305(const uint8_t key[32], const uint8_t *msg, size_t len, uint8_t tag[16]);
 
 long qo_aead_encrypt(int suite, const uint8_t *key, const uint8_t iv[12], const uint8_t *data,
                      size_t len, const uint8_t *aad, size_t alen, uint64_t pn, uint8_t *out);
