@@ -611,41 +611,40 @@ struct Gh5Grp {
             hi[i] = *(const u32x2 *)(base + kGh5Hi + w * 256 + a);
         }
     }
+    // acc ^= the group's entries, pairwise: one xor3 per dword and pair
     __device__ __forceinline__ void consume(u32x4 &acc) const
     {
         constexpr int n = W1 - W0;
+        static_assert(n % 2 == 0, "an odd window would cost four plain xors (kGh5Cut)");
 #pragma unroll
-        for (int i = 0; i + 1 < n; i += 2) {
+        for (int i = 0; i < n; i += 2) {
             acc.x = xor3(acc.x, lo[i].x, lo[i + 1].x);
             acc.y = xor3(acc.y, lo[i].y, lo[i + 1].y);
             acc.z = xor3(acc.z, hi[i].x, hi[i + 1].x);
             acc.w = xor3(acc.w, hi[i].y, hi[i + 1].y);
         }
-        if constexpr (n & 1) {
-            acc.x ^= lo[n - 1].x;
-            acc.y ^= lo[n - 1].y;
-            acc.z ^= hi[n - 1].x;
-            acc.w ^= hi[n - 1].y;
-        }
     }
 };
 
-// Six groups software-pipelined: group g + 1's reads are in flight while
-// group g is summed, so a multiply pays about one LDS round trip instead of
-// one per group; at most two groups' reads (<= 40 VGPRs) are held.  Grp: the
-// group type (Gh5Grp, Gh5GrpC), `in`: what its issue() takes.
+// Six groups (kGh5Cut, qpp_gh5.h: an even number of windows each, so the sum
+// is 13 xor3 per dword and nothing else) software-pipelined: group g + 1's
+// reads are in flight while group g is summed, so a multiply pays about one
+// LDS round trip instead of one per group; at most two groups' reads
+// (24 + 16 = 40 VGPRs) are held.  The sum starts from `init`, which costs
+// nothing: the result is init ^ x * H^4.  Grp: the group type (Gh5Grp,
+// Gh5GrpC), `in`: what its issue() takes.
 template <template <int, int> class Grp, class... In>
-__device__ __forceinline__ u32x4 gh5_pipeline(const In &...in)
+__device__ __forceinline__ u32x4 gh5_pipeline(u32x4 init, const In &...in)
 {
-    u32x4 acc = {0, 0, 0, 0};
+    u32x4 acc = init;
 #define QPP_SB() __builtin_amdgcn_sched_barrier(0)
     {
-        Grp<0, 5> a;
-        Grp<5, 9> b;
-        Grp<9, 14> c;
-        Grp<14, 18> d;
-        Grp<18, 22> e;
-        Grp<22, kGh5Windows> f;
+        Grp<kGh5Cut[0], kGh5Cut[1]> a;
+        Grp<kGh5Cut[1], kGh5Cut[2]> b;
+        Grp<kGh5Cut[2], kGh5Cut[3]> c;
+        Grp<kGh5Cut[3], kGh5Cut[4]> d;
+        Grp<kGh5Cut[4], kGh5Cut[5]> e;
+        Grp<kGh5Cut[5], kGh5Cut[6]> f;
         a.issue(in...);
         b.issue(in...);
         QPP_SB();
@@ -673,16 +672,23 @@ __device__ __forceinline__ u32x4 gh5_pipeline(const In &...in)
 #undef QPP_SB
     return acc;
 }
-__device__ __forceinline__ u32x4 ghash_mul_lds5(u32x4 x, const uint8_t *base, uint32_t tsel)
+// init ^ x * H^4
+__device__ __forceinline__ u32x4 ghash_mul_lds5(u32x4 x, const uint8_t *base, uint32_t tsel, u32x4 init = {0, 0, 0, 0})
 {
     const uint32_t xw[4] = {x.x, x.y, x.z, x.w};
-    return gh5_pipeline<Gh5Grp>(xw, base, tsel);
+    return gh5_pipeline<Gh5Grp>(init, xw, base, tsel);
 }
 
 // x * H^4 with the workgroup's LDS table entry at tsel
 __device__ __forceinline__ u32x4 ghash_mul_h4(u32x4 x, const uint8_t *base, uint32_t tsel)
 {
     return ghash_mul_lds5(x, base, tsel);
+}
+// init ^ (a ^ b) * H^4: the step loop's form (this table's addresses take the
+// windows of a ^ b itself, so that one xor stays)
+__device__ __forceinline__ u32x4 ghash_mul_h4(u32x4 a, u32x4 b, const uint8_t *base, uint32_t tsel, u32x4 init)
+{
+    return ghash_mul_lds5(a ^ b, base, tsel, init);
 }
 
 // The same multiply where the table sits at a compile-time LDS address (the
@@ -707,7 +713,14 @@ struct Gh5GrpC : Gh5Grp<W0, W1> {
 __device__ __forceinline__ u32x4 ghash_mul_lds5c(u32x4 x, const uint8_t *base)
 {
     const Gh5In in(x.x, x.y, x.z, x.w);
-    return gh5_pipeline<Gh5GrpC>(in, base);
+    return gh5_pipeline<Gh5GrpC>(u32x4{0, 0, 0, 0}, in, base);
+}
+// init ^ (a ^ b) * H^4: a ^ b is formed only inside the parity masks (Gh5In)
+__device__ __forceinline__ u32x4 ghash_mul_lds5c(u32x4 a, u32x4 b, const uint8_t *base, u32x4 init)
+{
+    const uint32_t aw[4] = {a.x, a.y, a.z, a.w}, bw[4] = {b.x, b.y, b.z, b.w};
+    const Gh5In in(aw, bw);
+    return gh5_pipeline<Gh5GrpC>(init, in, base);
 }
 
 // x * H^p from the slot's tables in global memory (tab = that power's 8 KiB):

@@ -640,8 +640,11 @@ __device__ __forceinline__ void write_header_v(const Pkt &P, int sub, bool maske
 //     range; a partial tail block is stored by its lane with byte stores), two
 //     H^4 multiplies.  BPL = 2: a wave whose lanes are all past the first step
 //     and at least three steps from their packet's end runs that step as a
-//     straight-line body of whole ciphertext blocks (inner2), any other
-//     wave-step with the per-lane block cases (step2).
+//     straight-line body of whole ciphertext blocks (inner2; the
+//     close-from-LDS form runs two of them per loop iteration while two
+//     remain), any other wave-step with the per-lane block cases (step2).
+//     The step's first multiply takes the second block as the seed of its
+//     window sum: acc = (x1 ^ (acc ^ x0) H^4) H^4 with no xor of its own.
 //   * Nothing of a packet waits in LDS: unprotect writes its header before the
 //     loop (the mask is known), protect in its first step (gcm_fast_hp) or
 //     after the loop; E_K(J0) stays in the lengths lane's registers.
@@ -678,6 +681,12 @@ __device__ __forceinline__ u32x4 gcm_packet(const Pkt &P, const KeySlot *ks, con
     auto mul_h4 = [&](u32x4 x) -> u32x4 {
         if constexpr (CLDS) return ghash_mul_lds5c(x, G.lds);
         else return ghash_mul_h4(x, G.lds, t4);
+    };
+    // init ^ (a ^ b) H^4: the sum of the window entries starts from init, and
+    // a ^ b is formed inside the address arithmetic where that is free
+    auto mul2_h4 = [&](u32x4 a, u32x4 b, u32x4 init) -> u32x4 {
+        if constexpr (CLDS) return ghash_mul_lds5c(a, b, G.lds, init);
+        else return ghash_mul_h4(a, b, G.lds, t4, init);
     };
     const u32x4 tiny_in = tiny ? ld_part(P.src, rlen) : zero4();
     const int q = pad + za;  // sequence position of CT block 0
@@ -840,7 +849,7 @@ __device__ __forceinline__ u32x4 gcm_packet(const Pkt &P, const KeySlot *ks, con
         __builtin_amdgcn_sched_barrier(0);
         // (0 ^ 0) H^4 = 0 over front padding
         if (first && pad >= 4) acc = x1;
-        else acc = mul_h4(acc ^ x0) ^ x1;
+        else acc = mul2_h4(acc, x0, x1);
         if (!last) acc = mul_h4(acc);
         else close(ks1);
     };
@@ -879,11 +888,11 @@ __device__ __forceinline__ u32x4 gcm_packet(const Pkt &P, const KeySlot *ks, con
             // 1200 bytes than the one general step it saves
             // (profiles/r17_gcm_interior_census.txt).
             constexpr int kInteriorK = 3;
-            auto inner2 = [&]() {
-                const u32x4 raw0 = nxt0, raw1 = nxt1;
+            // raw0, raw1: the step's input; n0, n1: where the next step's goes
+            auto inner2 = [&](const u32x4 raw0, const u32x4 raw1, u32x4 &n0, u32x4 &n1) {
                 const uint32_t lo = cin + 16u * (uint32_t)i;
-                nxt0 = __builtin_amdgcn_raw_buffer_load_b128(B.in, (int)(lo + 128u), 0, 0);
-                nxt1 = __builtin_amdgcn_raw_buffer_load_b128(B.in, (int)(lo + 192u), 0, 0);
+                n0 = __builtin_amdgcn_raw_buffer_load_b128(B.in, (int)(lo + 128u), 0, 0);
+                n1 = __builtin_amdgcn_raw_buffer_load_b128(B.in, (int)(lo + 192u), 0, 0);
                 const Te Tl = te_now();
                 u32x4 ks0, ks1;
                 aes_ctr2<NR>(cc, (uint32_t)(i + 2), (uint32_t)(i + 6), rk, Tl, ks0, ks1);
@@ -892,7 +901,7 @@ __device__ __forceinline__ u32x4 gcm_packet(const Pkt &P, const KeySlot *ks, con
                 __builtin_amdgcn_raw_buffer_store_b128(out0, B.out, (int)so, 0, 0);
                 __builtin_amdgcn_raw_buffer_store_b128(out1, B.out, (int)(so + 64u), 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
-                acc = mul_h4(mul_h4(acc ^ (ENC ? out0 : raw0)) ^ (ENC ? out1 : raw1));
+                acc = mul_h4(mul2_h4(acc, ENC ? out0 : raw0, ENC ? out1 : raw1));
                 i += 8;
             };
             QPP_PROBE_AT(4);
@@ -917,7 +926,21 @@ __device__ __forceinline__ u32x4 gcm_packet(const Pkt &P, const KeySlot *ks, con
                 // the straight-line body when every lane still in the loop is
                 // at an interior step (lanes whose packet has ended are
                 // inactive here and have no say): a scalar branch
-                if (__builtin_amdgcn_ballot_w64(k < kInteriorK) == 0) inner2();
+                // (close-from-LDS form: two of them per iteration where two
+                // remain, the prefetched input's two register sets swapping
+                // roles, so that the loop's phi copies are paid every other
+                // step; the 512-thread form, which sets its priority per
+                // iteration, loses by that: profiles/r17_gcm_interior_ab.txt)
+                if constexpr (CLDS) {
+                    if (__builtin_amdgcn_ballot_w64(k < kInteriorK + 1) == 0) {
+                        u32x4 a0, a1;
+                        inner2(nxt0, nxt1, a0, a1);
+                        --k;
+                        inner2(a0, a1, nxt0, nxt1);
+                        continue;
+                    }
+                }
+                if (__builtin_amdgcn_ballot_w64(k < kInteriorK) == 0) inner2(nxt0, nxt1, nxt0, nxt1);
                 else one2(k, std::false_type{});
             }
             if (!ENC) got_tag = nxt0;

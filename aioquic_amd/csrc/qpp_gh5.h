@@ -29,6 +29,13 @@ namespace qpp {
 constexpr int kGh5Windows = 26;
 constexpr int kGh5Hi = 27 * 256;  // offset of the high halves
 constexpr int kGh5Bytes = 14 * 1024;
+// A multiply reads and sums its windows in six groups, [kGh5Cut[g],
+// kGh5Cut[g + 1]) (gh5_pipeline, qpp_device.h).  Every group holds an even
+// number of windows: the sum takes its addends two at a time (one three-input
+// xor per dword and pair), so the 26 entries and a seed cost 13 operations
+// per dword; the first two groups together are the most that is held at once.
+constexpr int kGh5Groups = 6;
+constexpr int kGh5Cut[kGh5Groups + 1] = {0, 6, 10, 14, 18, 22, kGh5Windows};
 
 // the block whose window w holds e and whose other bits are zero (the table
 // entry (w, e) is this element times the power of H)
@@ -48,7 +55,8 @@ QPP_GH5_HD int gh5_word(int w, uint32_t e) { return w * 64 + 2 * (int)e; }
 // address (one entry per workgroup): its offset and the window's row ride in
 // the ds_read immediate, and the address proper is only e * 8.  The shift
 // rides in the extract: the block is split once into the bits of its
-// even-numbered windows and those of its odd-numbered ones (Gh5In: 8 v_and);
+// even-numbered windows and those of its odd-numbered ones (Gh5In: 8 v_and,
+// or 8 v_bitop3 that also take the xor of the two blocks it is made of);
 // for window w at bit `off` of word d, bits [off - 3, off) of copy w & 1
 // belong to window w - 1 and are zero there, so v_bfe(copy, off - 3, 8) is
 // e * 8 (off in 3..27: 21 windows; the 3-bit window 25 is one shift).  Window
@@ -61,11 +69,29 @@ constexpr uint32_t gh5_mask(int d, int parity)
         if ((((32 * d + b) / 5) & 1) == parity) m |= 1u << b;
     return m;
 }
+// (a ^ b) & m in one operation
+QPP_GH5_HD uint32_t gh5_xor_and(uint32_t a, uint32_t b, uint32_t m)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_bitop3_b32(a, b, m, 0x28);
+#else
+    return (a ^ b) & m;
+#endif
+}
 struct Gh5In {
     uint32_t m[2][4];  // [window parity][word]
     QPP_GH5_HD Gh5In(uint32_t x0, uint32_t x1, uint32_t x2, uint32_t x3)
         : m{{x0 & gh5_mask(0, 0), x1 & gh5_mask(1, 0), x2 & gh5_mask(2, 0), x3 & gh5_mask(3, 0)},
             {x0 & gh5_mask(0, 1), x1 & gh5_mask(1, 1), x2 & gh5_mask(2, 1), x3 & gh5_mask(3, 1)}}
+    {
+    }
+    // of the block a ^ b (the step loop's accumulator and its next input),
+    // which is never formed: the xor rides in the eight masks
+    QPP_GH5_HD Gh5In(const uint32_t (&a)[4], const uint32_t (&b)[4])
+        : m{{gh5_xor_and(a[0], b[0], gh5_mask(0, 0)), gh5_xor_and(a[1], b[1], gh5_mask(1, 0)),
+             gh5_xor_and(a[2], b[2], gh5_mask(2, 0)), gh5_xor_and(a[3], b[3], gh5_mask(3, 0))},
+            {gh5_xor_and(a[0], b[0], gh5_mask(0, 1)), gh5_xor_and(a[1], b[1], gh5_mask(1, 1)),
+             gh5_xor_and(a[2], b[2], gh5_mask(2, 1)), gh5_xor_and(a[3], b[3], gh5_mask(3, 1))}}
     {
     }
 };
