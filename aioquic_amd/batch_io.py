@@ -53,7 +53,7 @@ from .packet import decode_packet_number
 __all__ = ["SendBatch", "ReceiveBatch", "KeySlots", "setup_initial_batch", "ReservedBitsError",
            "ConnectionClosedError"]
 
-# host-side statuses of the C receive walks (_crypto_ext.c WALK_S_*)
+# host-side statuses of the C receive walks (csrc/qpp_rxwalk.h WALK_S_*)
 _S_RESERVED, _S_CLOSED = 0x101, 0x102
 _NO_CONN = 0xFFFFFFFF
 

@@ -49,12 +49,16 @@
 #include <Python.h>
 #include <ctype.h>
 #include <pthread.h>
+#include <stdarg.h>
 #include <string.h>
 
 #include "quic_pp.h"
+#include "qpp_rxwalk.h"
 
 static PyObject *g_crypto_error;
 static PyObject *g_aead_type, *g_hp_type, *g_kt_type, *g_plan_type, *g_multi_type, *g_cidmap_type;
+/* what the receive walks' records are made of: b"", -1, 0 and the drop reasons (module init) */
+static PyObject *g_empty, *g_minus1, *g_zero, *g_s_key, *g_s_dec, *g_s_rsv, *g_s_closed;
 
 /* ------------------------------------------------------------ sessions -- */
 
@@ -1086,58 +1090,108 @@ static PyObject *py_route(PyObject *m, PyObject *args)
     Py_RETURN_NONE;
 }
 
+
 /* route_unprotect_host(table, map, cid_len, offs_u64, lens_u32, data, conn_slot_u32, conn_expected_u64,
- *                      flags, out_len) -> (out, desc, route, results) */
-static PyObject *py_route_unprotect_host(PyObject *m, PyObject *args)
+ *                      flags, out_len) -> (out, desc, route, results)
+ * route_walk_unprotect_host(table, map, cid_len, offs_u64, lens_u32, data, long_idx_u32, conn_slot_u32 (x KEYSETS),
+ *                           conn_expected_u64 (x SPACES), flags, out_len)
+ *     -> (out, desc, route, results, walk, walk_n)
+ * route_phase_unprotect_host(table, map, cid_len, offs_u64, lens_u32, data, long_idx_u32, conn_slot_u32 (x KEYSETS),
+ *                            conn_expected_u64 (x SPACES), conn_next_u32 or None, flags, out_len)
+ *     -> (out, desc, route, results, walk, walk_n, phase)
+ * One wrapper, as qpp_route.hip's route_unprotect is one session call: the form (0 route, 1 + walk,
+ * 2 + walk and phase) says which arrays are parsed, which call runs and how many items come back. */
+static PyObject *route_unprotect_host(PyObject *args, int form)
 {
+    static const char *const refused[3] = {
+        "bad route arguments (cid_len outside 1..20, or a datagram outside the input or the output buffer); nothing "
+        "was launched",
+        "bad route arguments (cid_len outside 1..20, a datagram outside the input or the output buffer, or long_idx "
+        "not strictly increasing below n); nothing was launched",
+        "bad route arguments (cid_len outside 1..20, a datagram outside the input or the output buffer, long_idx not "
+        "strictly increasing below n, or a next-phase slot outside the table); nothing was launched"};
     PyObject *t, *mo;
-    const char *offs, *lens, *data, *cslot, *cexp;
-    Py_ssize_t l_offs, l_lens, l_data, l_cslot, l_cexp, out_len;
+    const char *offs, *lens, *data, *lidx = NULL, *cslot, *cexp, *cnext = NULL;
+    Py_ssize_t l_offs, l_lens, l_data, l_lidx = 0, l_cslot, l_cexp, l_cnext = 0, out_len;
     unsigned int cid_len, flags;
-    if (!PyArg_ParseTuple(args, "OOIy#y#y#y#y#In", &t, &mo, &cid_len, &offs, &l_offs, &lens, &l_lens, &data, &l_data,
-                          &cslot, &l_cslot, &cexp, &l_cexp, &flags, &out_len))
+    if (!(form == 0   ? PyArg_ParseTuple(args, "OOIy#y#y#y#y#In", &t, &mo, &cid_len, &offs, &l_offs, &lens, &l_lens,
+                                         &data, &l_data, &cslot, &l_cslot, &cexp, &l_cexp, &flags, &out_len)
+          : form == 1 ? PyArg_ParseTuple(args, "OOIy#y#y#y#y#y#In", &t, &mo, &cid_len, &offs, &l_offs, &lens, &l_lens,
+                                         &data, &l_data, &lidx, &l_lidx, &cslot, &l_cslot, &cexp, &l_cexp, &flags,
+                                         &out_len)
+                      : PyArg_ParseTuple(args, "OOIy#y#y#y#y#y#z#In", &t, &mo, &cid_len, &offs, &l_offs, &lens,
+                                         &l_lens, &data, &l_data, &lidx, &l_lidx, &cslot, &l_cslot, &cexp, &l_cexp,
+                                         &cnext, &l_cnext, &flags, &out_len)))
         return NULL;
     qpp_keytab *kt = as_table(t);
     qpp_cidmap *map = kt ? as_cidmap(mo) : NULL;
     if (!map) return NULL;
-    const Py_ssize_t n = l_lens / 4, nc = l_cslot / 4;
-    if (l_lens % 4 || l_cslot % 4 || l_offs != n * 8 || l_cexp != nc * 8 || out_len < 0 || flags > 0xffff ||
-        n > 0x7fffffff || nc > 0x7fffffff) {
+    /* the walking forms take a slot per key set and an expected number per space of each connection */
+    const Py_ssize_t per_slot = form ? 4 * QPP_KEYSETS : 4, per_exp = form ? 8 * QPP_SPACES : 8;
+    const Py_ssize_t n = l_lens / 4, nl = l_lidx / 4, nc = l_cslot / per_slot;
+    if (l_lens % 4 || l_lidx % 4 || l_cslot != nc * per_slot || l_offs != n * 8 || l_cexp != nc * per_exp ||
+        (cnext && l_cnext != nc * 4) || out_len < 0 || flags > 0xffff || n > 0x7fffffff || nc > 0x7fffffff ||
+        nl > 0x7fffffff || n + 3 * nl > 0x7fffffff) {
         PyErr_SetString(PyExc_ValueError, "bad array lengths, flags or output length");
         return NULL;
     }
-    PyObject *out = PyBytes_FromStringAndSize(NULL, out_len);
-    PyObject *desc = PyBytes_FromStringAndSize(NULL, n * (Py_ssize_t)sizeof(qpp_desc));
-    PyObject *route = PyBytes_FromStringAndSize(NULL, n * (Py_ssize_t)sizeof(qpp_route_rec));
-    PyObject *res = PyBytes_FromStringAndSize(NULL, n * (Py_ssize_t)sizeof(qpp_result));
-    PyObject *ret = NULL;
-    qpp_session *s = out && desc && route && res ? session() : NULL;
-    if (s) {
-        char *o = PyBytes_AsString(out);
-        /* an empty batch, or a refused one, leaves `out` as zeros */
-        memset(o, 0, (size_t)out_len);
-        int rc;
-        Py_BEGIN_ALLOW_THREADS
-        rc = qpp_session_route_unprotect(s, kt, map, cid_len, (const uint64_t *)offs, (const uint32_t *)lens,
-                                         (uint32_t)n, (const uint8_t *)data, (size_t)l_data,
-                                         (const uint32_t *)cslot, (const uint64_t *)cexp, (uint32_t)nc,
-                                         (uint16_t)flags, (uint8_t *)o, (size_t)out_len,
-                                         (qpp_desc *)PyBytes_AsString(desc),
-                                         (qpp_route_rec *)PyBytes_AsString(route),
-                                         (qpp_result *)PyBytes_AsString(res));
-        Py_END_ALLOW_THREADS
-        if (rc == QPP_E_ARG)
-            PyErr_SetString(PyExc_ValueError, "bad route arguments (cid_len outside 1..20, or a datagram outside "
-                                              "the input or the output buffer); nothing was launched");
-        else if (check_rc(rc) == 0)
-            ret = PyTuple_Pack(4, out, desc, route, res);
+    /* out, desc, route, results, then walk and walk_n, then phase */
+    const Py_ssize_t nd = n + 3 * nl, no = form == 0 ? 4 : form == 1 ? 6 : 7;
+    const Py_ssize_t size[7] = {out_len,
+                                nd * (Py_ssize_t)sizeof(qpp_desc),
+                                n * (Py_ssize_t)sizeof(qpp_route_rec),
+                                nd * (Py_ssize_t)sizeof(qpp_result),
+                                nl * QPP_WALK_MAX * (Py_ssize_t)sizeof(qpp_walk_rec),
+                                nl * 4,
+                                n};
+    PyObject *o[7] = {NULL};
+    char *b[7] = {NULL};
+    PyObject *ret = PyTuple_New(no);
+    for (Py_ssize_t k = 0; ret && k < no; ++k) {
+        o[k] = PyBytes_FromStringAndSize(NULL, size[k]);
+        if (!o[k] || PyTuple_SetItem(ret, k, o[k]) < 0) Py_CLEAR(ret);
+        else b[k] = PyBytes_AsString(o[k]);
     }
-    Py_XDECREF(out);
-    Py_XDECREF(desc);
-    Py_XDECREF(route);
-    Py_XDECREF(res);
+    qpp_session *s = ret ? session() : NULL;
+    if (!s) {
+        Py_XDECREF(ret);
+        return NULL;
+    }
+    /* an empty batch, or a refused one, leaves `out`, `walk` and `phase` as zeros */
+    memset(b[0], 0, (size_t)size[0]);
+    if (form >= 1) memset(b[4], 0, (size_t)size[4]);
+    if (form == 2) memset(b[6], 0, (size_t)size[6]);
+    int rc;
+    Py_BEGIN_ALLOW_THREADS
+    if (form == 0)
+        rc = qpp_session_route_unprotect(s, kt, map, cid_len, (const uint64_t *)offs, (const uint32_t *)lens,
+                                         (uint32_t)n, (const uint8_t *)data, (size_t)l_data, (const uint32_t *)cslot,
+                                         (const uint64_t *)cexp, (uint32_t)nc, (uint16_t)flags, (uint8_t *)b[0],
+                                         (size_t)out_len, (qpp_desc *)b[1], (qpp_route_rec *)b[2], (qpp_result *)b[3]);
+    else if (form == 1)
+        rc = qpp_session_route_walk_unprotect(s, kt, map, cid_len, (const uint64_t *)offs, (const uint32_t *)lens,
+                                              (uint32_t)n, (const uint8_t *)data, (size_t)l_data,
+                                              (const uint32_t *)lidx, (uint32_t)nl, (const uint32_t *)cslot,
+                                              (const uint64_t *)cexp, (uint32_t)nc, (uint16_t)flags, (uint8_t *)b[0],
+                                              (size_t)out_len, (qpp_desc *)b[1], (qpp_route_rec *)b[2],
+                                              (qpp_result *)b[3], (qpp_walk_rec *)b[4], (uint32_t *)b[5]);
+    else
+        rc = qpp_session_route_phase_unprotect(s, kt, map, cid_len, (const uint64_t *)offs, (const uint32_t *)lens,
+                                               (uint32_t)n, (const uint8_t *)data, (size_t)l_data,
+                                               (const uint32_t *)lidx, (uint32_t)nl, (const uint32_t *)cslot,
+                                               (const uint64_t *)cexp, (uint32_t)nc, (const uint32_t *)cnext,
+                                               (uint16_t)flags, (uint8_t *)b[0], (size_t)out_len, (qpp_desc *)b[1],
+                                               (qpp_route_rec *)b[2], (qpp_result *)b[3], (qpp_walk_rec *)b[4],
+                                               (uint32_t *)b[5], (uint8_t *)b[6]);
+    Py_END_ALLOW_THREADS
+    if (rc == QPP_E_ARG) PyErr_SetString(PyExc_ValueError, refused[form]);
+    if (rc == QPP_E_ARG || check_rc(rc) < 0) Py_CLEAR(ret);
     return ret;
 }
+
+static PyObject *py_route_unprotect_host(PyObject *m, PyObject *args) { return route_unprotect_host(args, 0); }
+static PyObject *py_route_walk_unprotect_host(PyObject *m, PyObject *args) { return route_unprotect_host(args, 1); }
+static PyObject *py_route_phase_unprotect_host(PyObject *m, PyObject *args) { return route_unprotect_host(args, 2); }
 
 /* route_walk(cid_len, off_ptr, len_ptr, n, in_ptr, route_ptr, long_ptr, n_long, slot_ptr, exp_ptr, n_conn, flags,
  *            desc_ptr, walk_ptr, walk_n_ptr, stream) */
@@ -1164,69 +1218,6 @@ static PyObject *py_route_walk(PyObject *m, PyObject *args)
     Py_RETURN_NONE;
 }
 
-/* route_walk_unprotect_host(table, map, cid_len, offs_u64, lens_u32, data, long_idx_u32, conn_slot_u32 (x KEYSETS),
- *                           conn_expected_u64 (x SPACES), flags, out_len)
- *     -> (out, desc, route, results, walk, walk_n) */
-static PyObject *py_route_walk_unprotect_host(PyObject *m, PyObject *args)
-{
-    PyObject *t, *mo;
-    const char *offs, *lens, *data, *lidx, *cslot, *cexp;
-    Py_ssize_t l_offs, l_lens, l_data, l_lidx, l_cslot, l_cexp, out_len;
-    unsigned int cid_len, flags;
-    if (!PyArg_ParseTuple(args, "OOIy#y#y#y#y#y#In", &t, &mo, &cid_len, &offs, &l_offs, &lens, &l_lens, &data, &l_data,
-                          &lidx, &l_lidx, &cslot, &l_cslot, &cexp, &l_cexp, &flags, &out_len))
-        return NULL;
-    qpp_keytab *kt = as_table(t);
-    qpp_cidmap *map = kt ? as_cidmap(mo) : NULL;
-    if (!map) return NULL;
-    const Py_ssize_t n = l_lens / 4, nl = l_lidx / 4, nc = l_cslot / (4 * QPP_KEYSETS);
-    if (l_lens % 4 || l_lidx % 4 || l_cslot != nc * 4 * QPP_KEYSETS || l_offs != n * 8 ||
-        l_cexp != nc * 8 * QPP_SPACES || out_len < 0 || flags > 0xffff || n > 0x7fffffff || nc > 0x7fffffff ||
-        nl > 0x7fffffff || n + 3 * nl > 0x7fffffff) {
-        PyErr_SetString(PyExc_ValueError, "bad array lengths, flags or output length");
-        return NULL;
-    }
-    const Py_ssize_t nd = n + 3 * nl;
-    PyObject *out = PyBytes_FromStringAndSize(NULL, out_len);
-    PyObject *desc = PyBytes_FromStringAndSize(NULL, nd * (Py_ssize_t)sizeof(qpp_desc));
-    PyObject *route = PyBytes_FromStringAndSize(NULL, n * (Py_ssize_t)sizeof(qpp_route_rec));
-    PyObject *res = PyBytes_FromStringAndSize(NULL, nd * (Py_ssize_t)sizeof(qpp_result));
-    PyObject *walk = PyBytes_FromStringAndSize(NULL, nl * QPP_WALK_MAX * (Py_ssize_t)sizeof(qpp_walk_rec));
-    PyObject *walk_n = PyBytes_FromStringAndSize(NULL, nl * 4);
-    PyObject *ret = NULL;
-    qpp_session *s = out && desc && route && res && walk && walk_n ? session() : NULL;
-    if (s) {
-        char *o = PyBytes_AsString(out);
-        /* an empty batch, or a refused one, leaves `out` as zeros */
-        memset(o, 0, (size_t)out_len);
-        memset(PyBytes_AsString(walk), 0, (size_t)PyBytes_Size(walk)); /* a refused call leaves zeros */
-        int rc;
-        Py_BEGIN_ALLOW_THREADS
-        rc = qpp_session_route_walk_unprotect(s, kt, map, cid_len, (const uint64_t *)offs, (const uint32_t *)lens,
-                                              (uint32_t)n, (const uint8_t *)data, (size_t)l_data,
-                                              (const uint32_t *)lidx, (uint32_t)nl, (const uint32_t *)cslot,
-                                              (const uint64_t *)cexp, (uint32_t)nc, (uint16_t)flags, (uint8_t *)o,
-                                              (size_t)out_len, (qpp_desc *)PyBytes_AsString(desc),
-                                              (qpp_route_rec *)PyBytes_AsString(route),
-                                              (qpp_result *)PyBytes_AsString(res),
-                                              (qpp_walk_rec *)PyBytes_AsString(walk),
-                                              (uint32_t *)PyBytes_AsString(walk_n));
-        Py_END_ALLOW_THREADS
-        if (rc == QPP_E_ARG)
-            PyErr_SetString(PyExc_ValueError, "bad route arguments (cid_len outside 1..20, a datagram outside the "
-                                              "input or the output buffer, or long_idx not strictly increasing "
-                                              "below n); nothing was launched");
-        else if (check_rc(rc) == 0)
-            ret = PyTuple_Pack(6, out, desc, route, res, walk, walk_n);
-    }
-    Py_XDECREF(out);
-    Py_XDECREF(desc);
-    Py_XDECREF(route);
-    Py_XDECREF(res);
-    Py_XDECREF(walk);
-    Py_XDECREF(walk_n);
-    return ret;
-}
 
 static PyObject *py_route_walk_launches(PyObject *m, PyObject *unused)
 {
@@ -1257,75 +1248,6 @@ static PyObject *py_route_phase_launches(PyObject *m, PyObject *unused)
     return PyLong_FromUnsignedLongLong(qpp_route_phase_launches());
 }
 
-/* route_phase_unprotect_host(table, map, cid_len, offs_u64, lens_u32, data, long_idx_u32, conn_slot_u32 (x KEYSETS),
- *                            conn_expected_u64 (x SPACES), conn_next_u32 or None, flags, out_len)
- *     -> (out, desc, route, results, walk, walk_n, phase) */
-static PyObject *py_route_phase_unprotect_host(PyObject *m, PyObject *args)
-{
-    PyObject *t, *mo;
-    const char *offs, *lens, *data, *lidx, *cslot, *cexp, *cnext = NULL;
-    Py_ssize_t l_offs, l_lens, l_data, l_lidx, l_cslot, l_cexp, l_cnext = 0, out_len;
-    unsigned int cid_len, flags;
-    if (!PyArg_ParseTuple(args, "OOIy#y#y#y#y#y#z#In", &t, &mo, &cid_len, &offs, &l_offs, &lens, &l_lens, &data,
-                          &l_data, &lidx, &l_lidx, &cslot, &l_cslot, &cexp, &l_cexp, &cnext, &l_cnext, &flags,
-                          &out_len))
-        return NULL;
-    qpp_keytab *kt = as_table(t);
-    qpp_cidmap *map = kt ? as_cidmap(mo) : NULL;
-    if (!map) return NULL;
-    const Py_ssize_t n = l_lens / 4, nl = l_lidx / 4, nc = l_cslot / (4 * QPP_KEYSETS);
-    if (l_lens % 4 || l_lidx % 4 || l_cslot != nc * 4 * QPP_KEYSETS || l_offs != n * 8 ||
-        l_cexp != nc * 8 * QPP_SPACES || (cnext && l_cnext != nc * 4) || out_len < 0 || flags > 0xffff ||
-        n > 0x7fffffff || nc > 0x7fffffff || nl > 0x7fffffff || n + 3 * nl > 0x7fffffff) {
-        PyErr_SetString(PyExc_ValueError, "bad array lengths, flags or output length");
-        return NULL;
-    }
-    const Py_ssize_t nd = n + 3 * nl;
-    PyObject *out = PyBytes_FromStringAndSize(NULL, out_len);
-    PyObject *desc = PyBytes_FromStringAndSize(NULL, nd * (Py_ssize_t)sizeof(qpp_desc));
-    PyObject *route = PyBytes_FromStringAndSize(NULL, n * (Py_ssize_t)sizeof(qpp_route_rec));
-    PyObject *res = PyBytes_FromStringAndSize(NULL, nd * (Py_ssize_t)sizeof(qpp_result));
-    PyObject *walk = PyBytes_FromStringAndSize(NULL, nl * QPP_WALK_MAX * (Py_ssize_t)sizeof(qpp_walk_rec));
-    PyObject *walk_n = PyBytes_FromStringAndSize(NULL, nl * 4);
-    PyObject *phase = PyBytes_FromStringAndSize(NULL, n);
-    PyObject *ret = NULL;
-    qpp_session *s = out && desc && route && res && walk && walk_n && phase ? session() : NULL;
-    if (s) {
-        char *o = PyBytes_AsString(out);
-        /* an empty batch, or a refused one, leaves `out` as zeros */
-        memset(o, 0, (size_t)out_len);
-        memset(PyBytes_AsString(walk), 0, (size_t)PyBytes_Size(walk));
-        memset(PyBytes_AsString(phase), 0, (size_t)n);
-        int rc;
-        Py_BEGIN_ALLOW_THREADS
-        rc = qpp_session_route_phase_unprotect(s, kt, map, cid_len, (const uint64_t *)offs, (const uint32_t *)lens,
-                                               (uint32_t)n, (const uint8_t *)data, (size_t)l_data,
-                                               (const uint32_t *)lidx, (uint32_t)nl, (const uint32_t *)cslot,
-                                               (const uint64_t *)cexp, (uint32_t)nc, (const uint32_t *)cnext,
-                                               (uint16_t)flags, (uint8_t *)o, (size_t)out_len,
-                                               (qpp_desc *)PyBytes_AsString(desc),
-                                               (qpp_route_rec *)PyBytes_AsString(route),
-                                               (qpp_result *)PyBytes_AsString(res),
-                                               (qpp_walk_rec *)PyBytes_AsString(walk),
-                                               (uint32_t *)PyBytes_AsString(walk_n),
-                                               (uint8_t *)PyBytes_AsString(phase));
-        Py_END_ALLOW_THREADS
-        if (rc == QPP_E_ARG)
-            PyErr_SetString(PyExc_ValueError, "bad route arguments (cid_len outside 1..20, a datagram outside the "
-                                              "input or the output buffer, long_idx not strictly increasing below "
-                                              "n, or a next-phase slot outside the table); nothing was launched");
-        else if (check_rc(rc) == 0)
-            ret = PyTuple_Pack(7, out, desc, route, res, walk, walk_n, phase);
-    }
-    Py_XDECREF(out);
-    Py_XDECREF(desc);
-    Py_XDECREF(route);
-    Py_XDECREF(res);
-    Py_XDECREF(walk);
-    Py_XDECREF(walk_n);
-    Py_XDECREF(phase);
-    return ret;
-}
 
 /* route_accept(off_ptr, len_ptr, n, in_ptr, route_ptr, long_ptr, n_long, walk_ptr, walk_n_ptr, row_ptr, slot_ptr,
  *              n_acc, accept_flags, desc_flags, ini_ptr, desc_ptr, acc_ptr, stream) */
@@ -1605,6 +1527,31 @@ static int check_len(Py_ssize_t len, Py_ssize_t n, Py_ssize_t size, const char *
     return -1;
 }
 
+/* The scratch of one call: every buffer it takes, released together.  A failed
+ * allocation is remembered, so a caller takes all it needs and asks once. */
+#define SCRATCH_MAX 32
+typedef struct {
+    void *p[SCRATCH_MAX];
+    int n, failed;
+} Scratch;
+
+static void *scratch_alloc(Scratch *s, size_t bytes, int zeroed)
+{
+    void *p = NULL;
+    if (s->n < SCRATCH_MAX) p = zeroed ? calloc(bytes ? bytes : 1, 1) : malloc(bytes ? bytes : 1);
+    if (p) s->p[s->n++] = p;
+    else s->failed = 1;
+    return p;
+}
+
+#define SCRATCH(s, type, count) ((type *)scratch_alloc((s), (size_t)(count) * sizeof(type), 0))
+#define SCRATCH0(s, type, count) ((type *)scratch_alloc((s), (size_t)(count) * sizeof(type), 1))
+
+static void scratch_free_all(Scratch *s)
+{
+    while (s->n) free(s->p[--s->n]);
+}
+
 /* protect_datagrams(table, plains, dg_u32, off_u32, hsize_u32, size_u32, pn_u64, slot_u32)
  *     -> (wire datagrams, results)
  * The deferred-encryption builder's flush (QuicPacketBuilder._end_packet,
@@ -1634,13 +1581,16 @@ static PyObject *py_protect_datagrams(PyObject *m, PyObject *args)
     plains = PySequence_Tuple(plains);
     if (!plains) return NULL;
     const Py_ssize_t nd = PyTuple_Size(plains);
-    PyObject *ret = NULL, *wires = NULL, *res = NULL;
-    size_t *base = NULL;
-    qpp_desc *desc = NULL;
-    base = (size_t *)malloc(((size_t)nd + 1) * sizeof(size_t));
-    desc = (qpp_desc *)calloc(n ? (size_t)n : 1, sizeof(qpp_desc));
-    res = PyBytes_FromStringAndSize(NULL, n * (Py_ssize_t)sizeof(qpp_result));
-    if (!base || !desc || !res) {
+    PyObject *ret = NULL, *wires = NULL;
+    Scratch sc = {{NULL}, 0, 0};
+    size_t *base = SCRATCH(&sc, size_t, nd + 1);
+    qpp_desc *desc = SCRATCH0(&sc, qpp_desc, n);
+    /* the copy jobs: datagram d between its bytes object and staging */
+    uint8_t **cd = SCRATCH(&sc, uint8_t *, nd + 1);
+    const uint8_t **cs = SCRATCH(&sc, const uint8_t *, nd + 1);
+    size_t *cl = SCRATCH(&sc, size_t, nd + 1);
+    PyObject *res = PyBytes_FromStringAndSize(NULL, n * (Py_ssize_t)sizeof(qpp_result));
+    if (sc.failed || !res) {
         PyErr_NoMemory();
         goto done;
     }
@@ -1677,15 +1627,6 @@ static PyObject *py_protect_datagrams(PyObject *m, PyObject *args)
         uint8_t *hin, *hout;
         if (!s || check_rc(qpp_session_stage(s, total ? total : 1, (uint32_t)(n ? n : 1), &hin, &hout)) < 0)
             goto done;
-        /* the copy jobs: datagram d between its bytes object and staging */
-        uint8_t **cd = (uint8_t **)malloc(((size_t)nd + 1) * sizeof(uint8_t *));
-        const uint8_t **cs = (const uint8_t **)malloc(((size_t)nd + 1) * sizeof(uint8_t *));
-        size_t *cl = (size_t *)malloc(((size_t)nd + 1) * sizeof(size_t));
-        if (!cd || !cs || !cl) {
-            free(cd), free(cs), free(cl);
-            PyErr_NoMemory();
-            goto done;
-        }
         for (Py_ssize_t d = 0; d < nd; ++d) {
             cd[d] = hin + base[d];
             cs[d] = (const uint8_t *)PyBytes_AsString(PyTuple_GetItem(plains, d));
@@ -1718,42 +1659,44 @@ static PyObject *py_protect_datagrams(PyObject *m, PyObject *args)
             Py_END_ALLOW_THREADS
             ret = PyTuple_Pack(2, wires, res);
         }
-        free(cd), free(cs), free(cl);
     }
 done:
     Py_XDECREF(wires);
     Py_XDECREF(res);
     Py_DECREF(plains);
-    free(base);
-    free(desc);
+    scratch_free_all(&sc);
     return ret;
 }
 
-/* Host-side outcomes of the receive walks (never produced by a kernel):
- * a packet that authenticated with a reserved bit set (connection.py:949-960),
- * a packet of a connection the walk has closed (:756-757). */
-#define WALK_S_RESERVED 0x101
-#define WALK_S_CLOSED 0x102
-#define WALK_NO_CONN 0xffffffffu
 /* receive_short's slot_of: closed on entry / no receive key (no launch) */
 #define RS_CLOSED 0xfffffffeu
 
-/* decode_packet_number (quic/packet.py:118-132) of the truncated number as
- * HeaderProtection.remove hands it over: a signed C int (_crypto.c:349), so a
- * 4-byte value >= 2^31 enters negative, exactly as the Python walk sees it.
- * Returns -1 where Python would produce a negative number. */
-static int64_t decode_pn_signed(uint64_t pn, int pn_len, uint64_t expected)
+/* What a walk starts from and hands back: copies of the caller's expected
+ * numbers and closed flags for qpp_rxwalk.h's rule to update, nothing blocked. */
+typedef struct {
+    RxWalkState st;
+    PyObject *sexp, *closed;
+} WalkState;
+
+static int walk_state_init(WalkState *ws, Scratch *sc, const char *a_sexp, Py_ssize_t l_sexp, const char *a_closed,
+                           Py_ssize_t l_closed, size_t n_pairs)
 {
-    const int bits = 8 * pn_len;
-    int64_t trunc = (int64_t)(pn & ((1ull << bits) - 1));
-    if (pn_len == 4 && trunc >= ((int64_t)1 << 31)) trunc -= (int64_t)1 << 32;
-    const int64_t window = (int64_t)1 << bits, half = window / 2, exp = (int64_t)expected;
-    const int64_t cand = (exp & ~(window - 1)) | trunc;
-    int64_t r;
-    if (cand <= exp - half && cand < ((int64_t)1 << 62) - window) r = cand + window;
-    else if (cand > exp + half && cand >= window) r = cand - window;
-    else r = cand;
-    return r < 0 ? -1 : r;
+    ws->sexp = PyBytes_FromStringAndSize(a_sexp, l_sexp);
+    ws->closed = PyBytes_FromStringAndSize(a_closed, l_closed);
+    if (!ws->sexp || !ws->closed) return -1;
+    ws->st.sx = (uint64_t *)PyBytes_AsString(ws->sexp);
+    ws->st.closed = (uint8_t *)PyBytes_AsString(ws->closed);
+    ws->st.blocked_pair = SCRATCH0(sc, uint8_t, n_pairs);
+    ws->st.blocked_space = SCRATCH0(sc, uint8_t, l_sexp / 8);
+    ws->st.blocked_conn = SCRATCH0(sc, uint8_t, l_closed);
+    ws->st.rolled = NULL;
+    return sc->failed ? (PyErr_NoMemory(), -1) : 0;
+}
+
+static void walk_state_clear(WalkState *ws)
+{
+    Py_CLEAR(ws->sexp);
+    Py_CLEAR(ws->closed);
 }
 
 /* The in-order walk of unprotect_walk / walk_results over the results of one
@@ -1764,78 +1707,69 @@ typedef struct {
     const uint32_t *slots, *offs, *pair, *space, *conn;
     const uint64_t *exp, *out_off;
     const uint8_t *track, *rsv, *hout;
-    uint64_t *sx;
-    uint8_t *closed, *blocked_pair, *blocked_space, *blocked_conn;
+    RxWalkState *st;
     PyObject *outs, *deferred;
 } ResultsWalk;
 
 static int results_walk(const ResultsWalk *w, qpp_result *r)
 {
-    const Py_ssize_t n = w->n;
-    const uint32_t *slots = w->slots, *offs = w->offs, *pair = w->pair, *space = w->space, *conn = w->conn;
-    const uint64_t *exp = w->exp, *out_off = w->out_off;
-    const uint8_t *track = w->track, *rsv = w->rsv, *hout = w->hout;
-    uint64_t *sx = w->sx;
-    uint8_t *closed = w->closed, *blocked_pair = w->blocked_pair, *blocked_space = w->blocked_space;
-    uint8_t *blocked_conn = w->blocked_conn;
-    PyObject *outs = w->outs, *deferred = w->deferred;
     /* no receive key (crypto.py:78-79) and packet-number offsets past the
        header limit fail whatever the launch left in their results */
-    for (Py_ssize_t i = 0; i < n; ++i) {
-        if (slots[i] == 0xffffffffu) r[i].status = QPP_S_NO_KEY;
-        else if (offs[i] > QPP_MAX_HDR) r[i].status = QPP_S_LENGTH;
+    for (Py_ssize_t i = 0; i < w->n; ++i) {
+        if (w->slots[i] == 0xffffffffu) r[i].status = QPP_S_NO_KEY;
+        else if (w->offs[i] > QPP_MAX_HDR) r[i].status = QPP_S_LENGTH;
     }
-    for (Py_ssize_t i = 0; i < n; ++i) {
-        const uint32_t p = pair[i], sp = space[i], c = conn[i];
-        PyObject *item = Py_None;
+    for (Py_ssize_t i = 0; i < w->n; ++i) {
+        RxWalkPacket f = {.pair = w->pair[i], .space = w->space[i], .conn = w->conn[i], .launched = 1,
+                          .status = r[i].status, .hdr_len = r[i].hdr_len, .pn = r[i].pn, .pn_off = w->offs[i],
+                          .exp = w->exp[i], .rsv_mask = w->rsv[i], .track = w->track[i], .phase = RXWALK_NO_PHASE};
+        const uint8_t *o = f.status == QPP_S_OK ? w->hout + w->out_off[i] : NULL;
+        if (o && f.hdr_len) f.first = o[0];
         Py_INCREF(Py_None);
-        PyList_SetItem(outs, i, item);
-        int defer = blocked_pair[p] || blocked_space[sp] || (c != WALK_NO_CONN && blocked_conn[c]);
-        if (!defer && c != WALK_NO_CONN && closed[c]) {
-            r[i].status = WALK_S_CLOSED; /* connection.py:756-757 */
-            continue;
-        }
-        const uint16_t st = r[i].status;
-        const uint64_t now = sx[sp];
-        if (!defer && st == QPP_S_KEY_PHASE) defer = 1;
-        if (!defer && now != exp[i] && (st == QPP_S_OK || st == QPP_S_DECRYPT)) {
-            const int pn_len = (int)r[i].hdr_len - (int)offs[i];
-            if (pn_len < 1 || pn_len > 4 || decode_pn_signed(r[i].pn, pn_len, now) != (int64_t)r[i].pn) defer = 1;
-        }
-        if (defer) {
-            blocked_pair[p] = blocked_space[sp] = 1;
-            if (c != WALK_NO_CONN) blocked_conn[c] = 1;
+        PyList_SetItem(w->outs, i, Py_None);
+        switch (rxwalk_step(w->st, &f)) {
+        case RXW_DEFERRED: {
             PyObject *ix = PyLong_FromSsize_t(i);
-            if (!ix || PyList_Append(deferred, ix) < 0) {
-                Py_XDECREF(ix);
-                return -1;
-            }
-            Py_DECREF(ix);
-            continue;
+            const int bad = ix ? PyList_Append(w->deferred, ix) : -1;
+            Py_XDECREF(ix);
+            if (bad < 0) return -1;
+            break;
         }
-        if (st != QPP_S_OK) continue;
-        const uint8_t *o = hout + out_off[i];
-        if (rsv[i] && r[i].hdr_len && (o[0] & rsv[i])) {
-            /* connection.py:949-960: close, end, no expected-number update */
-            r[i].status = WALK_S_RESERVED;
-            if (c != WALK_NO_CONN) closed[c] = 1;
-            continue;
+        case RXW_CLOSED: r[i].status = WALK_S_CLOSED; break;
+        case RXW_RESERVED: r[i].status = WALK_S_RESERVED; break;
+        case RXW_OK: {
+            PyObject *h = PyBytes_FromStringAndSize((const char *)o, f.hdr_len);
+            PyObject *pl = PyBytes_FromStringAndSize((const char *)o + f.hdr_len, (Py_ssize_t)r[i].out_len - f.hdr_len);
+            PyObject *pn = PyLong_FromUnsignedLongLong(f.pn);
+            PyObject *item = (h && pl && pn) ? PyTuple_Pack(3, h, pl, pn) : NULL;
+            Py_XDECREF(h);
+            Py_XDECREF(pl);
+            Py_XDECREF(pn);
+            if (!item) return -1;
+            PyObject_GC_UnTrack(item); /* bytes and an int: never in a cycle (make_record) */
+            PyList_SetItem(w->outs, i, item);
+            break;
         }
-        PyObject *h = PyBytes_FromStringAndSize((const char *)o, r[i].hdr_len);
-        PyObject *pl = PyBytes_FromStringAndSize((const char *)o + r[i].hdr_len,
-                                                 (Py_ssize_t)r[i].out_len - r[i].hdr_len);
-        PyObject *pn = PyLong_FromUnsignedLongLong(r[i].pn);
-        item = (h && pl && pn) ? PyTuple_Pack(3, h, pl, pn) : NULL;
-        Py_XDECREF(h);
-        Py_XDECREF(pl);
-        Py_XDECREF(pn);
-        if (!item) return -1;
-        PyObject_GC_UnTrack(item); /* bytes and an int: never in a cycle (make_record) */
-        PyList_SetItem(outs, i, item);
-        if (track[i] && r[i].pn > now) sx[sp] = r[i].pn + 1;
+        default: break; /* no key, or failed: the status says which */
+        }
     }
     return 0;
 }
+
+/* The per-packet arrays of unprotect_walk and walk_results hold n items each. */
+static int walk_lens_ok(Py_ssize_t n, Py_ssize_t l_sl, Py_ssize_t l_exp, Py_ssize_t l_offs, Py_ssize_t l_pair,
+                        Py_ssize_t l_space, Py_ssize_t l_track, Py_ssize_t l_conn, Py_ssize_t l_rsv, Py_ssize_t l_sexp)
+{
+    if (l_sexp % 8) {
+        PyErr_SetString(PyExc_ValueError, "space_exp: whole u64 items");
+        return 0;
+    }
+    return check_len(l_sl, n, 4, "slots") == 0 && check_len(l_exp, n, 8, "exp") == 0 &&
+           check_len(l_offs, n, 4, "offs") == 0 && check_len(l_pair, n, 4, "pair") == 0 &&
+           check_len(l_space, n, 4, "space") == 0 && check_len(l_track, n, 1, "track") == 0 &&
+           check_len(l_conn, n, 4, "conn") == 0 && check_len(l_rsv, n, 1, "rsv") == 0;
+}
+
 
 /* unprotect_walk(table, slots_u32, exp_u64, packets, offs_u32, pair_u32,
  *                space_u32, track_u8, space_exp_u64, n_pairs, conn_u32,
@@ -1877,25 +1811,15 @@ static PyObject *py_unprotect_walk(PyObject *m, PyObject *args)
     qpp_keytab *kt = as_table(t);
     if (!kt) return NULL;
     const Py_ssize_t n = PyList_Size(packets);
-    if (check_len(l_sl, n, 4, "slots") < 0 || check_len(l_exp, n, 8, "exp") < 0 ||
-        check_len(l_offs, n, 4, "offs") < 0 || check_len(l_pair, n, 4, "pair") < 0 ||
-        check_len(l_space, n, 4, "space") < 0 || check_len(l_track, n, 1, "track") < 0 ||
-        check_len(l_conn, n, 4, "conn") < 0 || check_len(l_rsv, n, 1, "rsv") < 0 || l_sexp % 8)
-        return l_sexp % 8 ? (PyErr_SetString(PyExc_ValueError, "space_exp: whole u64 items"), NULL) : NULL;
+    if (!walk_lens_ok(n, l_sl, l_exp, l_offs, l_pair, l_space, l_track, l_conn, l_rsv, l_sexp)) return NULL;
     const Py_ssize_t n_spaces = l_sexp / 8, n_conns = l_closed;
     const uint32_t *slots = (const uint32_t *)a_sl, *offs = (const uint32_t *)a_offs, *pair = (const uint32_t *)a_pair,
                    *space = (const uint32_t *)a_space, *conn = (const uint32_t *)a_conn;
     const uint64_t *exp = (const uint64_t *)a_exp;
-    const uint8_t *track = (const uint8_t *)a_track, *rsv = (const uint8_t *)a_rsv;
-    PyObject *ret = NULL, *outs = NULL, *res = NULL, *deferred = NULL, *sexp_out = NULL, *closed_out = NULL;
-    qpp_desc *desc = NULL;
-    uint64_t *out_off = NULL;
-    uint8_t *blocked_pair = NULL, *blocked_space = NULL, *blocked_conn = NULL;
-    sexp_out = PyBytes_FromStringAndSize(a_sexp, l_sexp);  /* the spaces' expected numbers, advanced below */
-    closed_out = PyBytes_FromStringAndSize(a_closed, l_closed); /* the connections' closed flags, set below */
-    if (!sexp_out || !closed_out) goto done;
-    uint64_t *sx = (uint64_t *)PyBytes_AsString(sexp_out);
-    uint8_t *closed = (uint8_t *)PyBytes_AsString(closed_out);
+    PyObject *ret = NULL, *outs = NULL, *res = NULL, *deferred = NULL;
+    Scratch sc = {{NULL}, 0, 0};
+    WalkState ws;
+    if (walk_state_init(&ws, &sc, a_sexp, l_sexp, a_closed, l_closed, n_pairs) < 0) goto done;
     for (Py_ssize_t i = 0; i < n; ++i)
         if (pair[i] >= n_pairs || (Py_ssize_t)space[i] >= n_spaces ||
             (conn[i] != WALK_NO_CONN && (Py_ssize_t)conn[i] >= n_conns)) {
@@ -1912,15 +1836,12 @@ static PyObject *py_unprotect_walk(PyObject *m, PyObject *args)
         }
         total += (size_t)PyBytes_Size(o);
     }
-    desc = (qpp_desc *)calloc(n ? (size_t)n : 1, sizeof(qpp_desc));
-    out_off = (uint64_t *)calloc(n ? (size_t)n : 1, sizeof(uint64_t));
+    qpp_desc *desc = SCRATCH0(&sc, qpp_desc, n);
+    uint64_t *out_off = SCRATCH0(&sc, uint64_t, n);
     res = PyBytes_FromStringAndSize(NULL, n * (Py_ssize_t)sizeof(qpp_result));
-    blocked_pair = (uint8_t *)calloc(n_pairs ? n_pairs : 1, 1);
-    blocked_space = (uint8_t *)calloc(n_spaces ? (size_t)n_spaces : 1, 1);
-    blocked_conn = (uint8_t *)calloc(n_conns ? (size_t)n_conns : 1, 1);
     outs = PyList_New(n);
     deferred = PyList_New(0);
-    if (!desc || !out_off || !res || !blocked_pair || !blocked_space || !blocked_conn || !outs || !deferred) {
+    if (sc.failed || !res || !outs || !deferred) {
         PyErr_NoMemory();
         goto done;
     }
@@ -1944,22 +1865,17 @@ static PyObject *py_unprotect_walk(PyObject *m, PyObject *args)
         if (host_call(0, kt, desc, (uint32_t)n, hin, total, hout, total, PyBytes_AsString(res)) < 0) goto done;
     }
     {
-        const ResultsWalk w = {n, slots, offs, pair, space, conn, exp, out_off, track, rsv, hout, sx, closed,
-                               blocked_pair, blocked_space, blocked_conn, outs, deferred};
+        const ResultsWalk w = {n, slots, offs, pair, space, conn, exp, out_off, (const uint8_t *)a_track,
+                               (const uint8_t *)a_rsv, hout, &ws.st, outs, deferred};
         if (results_walk(&w, (qpp_result *)PyBytes_AsString(res)) < 0) goto done;
     }
-    ret = PyTuple_Pack(5, outs, res, deferred, sexp_out, closed_out);
+    ret = PyTuple_Pack(5, outs, res, deferred, ws.sexp, ws.closed);
 done:
-    Py_XDECREF(sexp_out);
-    Py_XDECREF(closed_out);
+    walk_state_clear(&ws);
     Py_XDECREF(outs);
     Py_XDECREF(res);
     Py_XDECREF(deferred);
-    free(desc);
-    free(out_off);
-    free(blocked_pair);
-    free(blocked_space);
-    free(blocked_conn);
+    scratch_free_all(&sc);
     return ret;
 }
 
@@ -1990,28 +1906,20 @@ static PyObject *py_walk_results(PyObject *m, PyObject *args)
         PyErr_SetString(PyExc_ValueError, "dix: whole u32 items; desc and results: as many whole records");
         return NULL;
     }
-    if (check_len(l_sl, n, 4, "slots") < 0 || check_len(l_exp, n, 8, "exp") < 0 ||
-        check_len(l_offs, n, 4, "offs") < 0 || check_len(l_pair, n, 4, "pair") < 0 ||
-        check_len(l_space, n, 4, "space") < 0 || check_len(l_track, n, 1, "track") < 0 ||
-        check_len(l_conn, n, 4, "conn") < 0 || check_len(l_rsv, n, 1, "rsv") < 0 || l_sexp % 8)
-        return l_sexp % 8 ? (PyErr_SetString(PyExc_ValueError, "space_exp: whole u64 items"), NULL) : NULL;
+    if (!walk_lens_ok(n, l_sl, l_exp, l_offs, l_pair, l_space, l_track, l_conn, l_rsv, l_sexp)) return NULL;
     const Py_ssize_t n_spaces = l_sexp / 8, n_conns = l_closed;
     const uint32_t *pair = (const uint32_t *)a_pair, *space = (const uint32_t *)a_space,
                    *conn = (const uint32_t *)a_conn, *dix = (const uint32_t *)a_dix;
     const qpp_desc *desc = (const qpp_desc *)a_desc;
     const qpp_result *rin = (const qpp_result *)a_res;
-    PyObject *ret = NULL, *outs = NULL, *res = NULL, *deferred = NULL, *sexp_out = NULL, *closed_out = NULL;
-    uint64_t *out_off = (uint64_t *)calloc(n ? (size_t)n : 1, sizeof(uint64_t));
-    uint8_t *blocked_pair = (uint8_t *)calloc(n_pairs ? n_pairs : 1, 1);
-    uint8_t *blocked_space = (uint8_t *)calloc(n_spaces ? (size_t)n_spaces : 1, 1);
-    uint8_t *blocked_conn = (uint8_t *)calloc(n_conns ? (size_t)n_conns : 1, 1);
-    sexp_out = PyBytes_FromStringAndSize(a_sexp, l_sexp);
-    closed_out = PyBytes_FromStringAndSize(a_closed, l_closed);
-    res = PyBytes_FromStringAndSize(NULL, n * (Py_ssize_t)sizeof(qpp_result));
-    outs = PyList_New(n);
-    deferred = PyList_New(0);
-    if (!out_off || !blocked_pair || !blocked_space || !blocked_conn || !sexp_out || !closed_out || !res || !outs ||
-        !deferred) {
+    Scratch sc = {{NULL}, 0, 0};
+    WalkState ws;
+    uint64_t *out_off = SCRATCH0(&sc, uint64_t, n);
+    PyObject *ret = NULL;
+    PyObject *res = PyBytes_FromStringAndSize(NULL, n * (Py_ssize_t)sizeof(qpp_result));
+    PyObject *outs = PyList_New(n), *deferred = PyList_New(0);
+    if (walk_state_init(&ws, &sc, a_sexp, l_sexp, a_closed, l_closed, n_pairs) < 0) goto done;
+    if (!res || !outs || !deferred) {
         PyErr_NoMemory();
         goto done;
     }
@@ -2034,22 +1942,16 @@ static PyObject *py_walk_results(PyObject *m, PyObject *args)
     {
         const ResultsWalk w = {n, (const uint32_t *)a_sl, (const uint32_t *)a_offs, pair, space, conn,
                                (const uint64_t *)a_exp, out_off, (const uint8_t *)a_track, (const uint8_t *)a_rsv,
-                               (const uint8_t *)a_out, (uint64_t *)PyBytes_AsString(sexp_out),
-                               (uint8_t *)PyBytes_AsString(closed_out), blocked_pair, blocked_space, blocked_conn, outs,
-                               deferred};
+                               (const uint8_t *)a_out, &ws.st, outs, deferred};
         if (results_walk(&w, r) < 0) goto done;
     }
-    ret = PyTuple_Pack(5, outs, res, deferred, sexp_out, closed_out);
+    ret = PyTuple_Pack(5, outs, res, deferred, ws.sexp, ws.closed);
 done:
-    Py_XDECREF(sexp_out);
-    Py_XDECREF(closed_out);
+    walk_state_clear(&ws);
     Py_XDECREF(outs);
     Py_XDECREF(res);
     Py_XDECREF(deferred);
-    free(out_off);
-    free(blocked_pair);
-    free(blocked_space);
-    free(blocked_conn);
+    scratch_free_all(&sc);
     return ret;
 }
 
@@ -2170,130 +2072,84 @@ typedef struct {
     const qpp_desc *desc;
     const qpp_result *res;
     const uint8_t *hout;
-    uint64_t *sx;     /* expected packet number per space, updated */
-    uint8_t *closed;  /* per connection, updated */
-    uint8_t *blocked_pair, *blocked_space, *blocked_conn;
+    RxWalkState *st;
+    /* receive_routed_phase (NULL otherwise, as st->rolled is): qpp_route_phase's verdict per descriptor */
+    const uint8_t *phase;
     PyObject *recs, *deferred;
     PyTypeObject *tp;
     allocfunc alloc;
-    PyObject *ptype, *epoch, *empty, *minus1, *zero, *s_key, *s_dec, *s_rsv, *s_closed;
+    PyObject *ptype, *epoch;
     /* output copies: header and payload of every packet, for the caller's par_copy */
     uint8_t **od;
     const uint8_t **os_;
     size_t *ol, on, otot;
-    /* receive_routed_phase (both NULL otherwise): qpp_route_phase's verdict per descriptor, and per pair
-       whether a packet of the batch has rolled its keys (updated) */
-    const uint8_t *phase;
-    uint8_t *rolled;
 } ShortWalk;
+
+/* the record of a datagram that yields no packet */
+static PyObject *drop_record(const ShortWalk *w, PyObject *di, PyObject *epoch, PyObject *why)
+{
+    PyObject *f[9] = {di, g_zero, Py_None, w->ptype, epoch, g_empty, g_empty, g_minus1, why};
+    return make_record(w->tp, w->alloc, f, 9);
+}
 
 static int short_walk(ShortWalk *w)
 {
-    const Py_ssize_t n = w->n;
-    const uint32_t *conn_of = w->conn_of, *slot_of = w->slot_of, *cpair = w->cpair, *cspace = w->cspace;
-    const qpp_desc *desc = w->desc;
-    const uint8_t *hout = w->hout;
-    uint8_t *blocked_pair = w->blocked_pair, *blocked_space = w->blocked_space, *blocked_conn = w->blocked_conn;
-    PyObject *recs = w->recs, *deferred = w->deferred, *ptype = w->ptype, *epoch = w->epoch, *empty = w->empty;
-    PyObject *minus1 = w->minus1, *zero = w->zero, *s_key = w->s_key, *s_dec = w->s_dec, *s_rsv = w->s_rsv;
-    PyObject *s_closed = w->s_closed;
-    PyTypeObject *tp = w->tp;
-    allocfunc alloc = w->alloc;
-    uint8_t **od = w->od;
-    const uint8_t **os_ = w->os_;
-    size_t *ol = w->ol, on = w->on, otot = w->otot;
-    int rc = -1;
-    {
-        uint64_t *sx = w->sx;
-        uint8_t *closed = w->closed;
-        const qpp_result *r = w->res;
-        uint32_t k = 0;
-        for (Py_ssize_t i = 0; i < n; ++i) {
-            PyObject *di = PyLong_FromSsize_t(w->dg ? (Py_ssize_t)w->dg[i] : i);
-            if (!di) goto done;
-            const uint32_t c = conn_of[i], p = cpair[c], sp = cspace[c];
-            const int launched = slot_of[i] < RS_CLOSED;
-            const uint32_t x = w->rix ? w->rix[i] : k;
-            const qpp_result *ri = launched ? &r[x] : NULL;
-            const qpp_desc *dk = launched ? &desc[x] : NULL;
-            k += launched;
-            /* a deferred packet of the connection may close it: wait for it */
-            int defer = blocked_conn[c];
-            if (!defer && launched) {
-                const uint64_t now = sx[sp];
-                defer = blocked_pair[p] || blocked_space[sp] || (!closed[c] && ri->status == QPP_S_KEY_PHASE);
-                /* the pair has rolled and this packet ran on the slot of the phase before: the general
-                   path's, as a flip is (it tries the phase after next and fails, crypto.py:91-96) */
-                if (!defer && !closed[c] && w->rolled && w->rolled[p] && !w->phase[x]) defer = 1;
-                if (!defer && !closed[c] && now != dk->pn && (ri->status == QPP_S_OK || ri->status == QPP_S_DECRYPT)) {
-                    const int pn_len = (int)ri->hdr_len - (int)dk->hdr_len;
-                    if (pn_len < 1 || pn_len > 4 || decode_pn_signed(ri->pn, pn_len, now) != (int64_t)ri->pn)
-                        defer = 1;
-                }
-            }
-            if (defer) {
-                blocked_conn[c] = 1;
-                if (launched) blocked_pair[p] = blocked_space[sp] = 1;
-                PyObject *dj = w->dg ? PyLong_FromSsize_t(i) : di;
-                const int bad = dj ? PyList_Append(deferred, dj) : -1;
-                if (w->dg) Py_XDECREF(dj);
-                Py_INCREF(Py_None);
-                PyList_SetItem(recs, i, Py_None);
-                Py_DECREF(di);
-                if (bad < 0) goto done;
-                continue;
-            }
-            PyObject *rec = NULL;
-            if (closed[c]) {
-                /* connection.py:756-757 */
-                PyObject *f[9] = {di, zero, Py_None, ptype, Py_None, empty, empty, minus1, s_closed};
-                rec = make_record(tp, alloc, f, 9);
-            } else if (!launched) {
-                PyObject *f[9] = {di, zero, Py_None, ptype, epoch, empty, empty, minus1, s_key};
-                rec = make_record(tp, alloc, f, 9);
-            } else {
-                const uint64_t now = sx[sp];
-                /* a packet of the next phase that authenticates updates the keys inside decrypt_packet
-                   (crypto.py:184-192), before the reserved bits are looked at (connection.py:949-960) */
-                if (w->rolled && w->phase[x] && ri->status == QPP_S_OK) w->rolled[p] = 1;
-                if (ri->status == QPP_S_OK && (hout[dk->out_off] & 0x18)) {
-                    /* connection.py:949-960: the close, before :984-985 */
-                    closed[c] = 1;
-                    PyObject *f[9] = {di, zero, Py_None, ptype, epoch, empty, empty, minus1, s_rsv};
-                    rec = make_record(tp, alloc, f, 9);
-                } else if (ri->status == QPP_S_OK) {
-                    const uint8_t *o = hout + dk->out_off;
-                    const size_t pll = (size_t)ri->out_len - ri->hdr_len;
-                    PyObject *h = PyBytes_FromStringAndSize(NULL, ri->hdr_len);
-                    PyObject *pl = PyBytes_FromStringAndSize(NULL, (Py_ssize_t)pll);
-                    PyObject *pn = PyLong_FromUnsignedLongLong(ri->pn);
-                    if (h && pl && pn) {
-                        od[on] = (uint8_t *)PyBytes_AsString(h), os_[on] = o, ol[on++] = ri->hdr_len;
-                        od[on] = (uint8_t *)PyBytes_AsString(pl), os_[on] = o + ri->hdr_len, ol[on++] = pll;
-                        otot += ri->hdr_len + pll;
-                        PyObject *f[9] = {di, zero, Py_None, ptype, epoch, h, pl, pn, Py_None};
-                        rec = make_record(tp, alloc, f, 9);
-                    }
-                    Py_XDECREF(h);
-                    Py_XDECREF(pl);
-                    Py_XDECREF(pn);
-                    if (ri->pn > now) sx[sp] = ri->pn + 1;
-                } else {
-                    PyObject *f[9] = {di, zero, Py_None, ptype, epoch, empty, empty, minus1,
-                                      ri->status == QPP_S_NO_KEY ? s_key : s_dec};
-                    rec = make_record(tp, alloc, f, 9);
-                }
-            }
-            Py_DECREF(di);
-            if (!rec) goto done;
-            PyList_SetItem(recs, i, rec);
+    uint32_t k = 0;
+    for (Py_ssize_t i = 0; i < w->n; ++i) {
+        const uint32_t c = w->conn_of[i];
+        RxWalkPacket f = {.pair = w->cpair[c], .space = w->cspace[c], .conn = c, .launched = w->slot_of[i] < RS_CLOSED,
+                          .rsv_mask = 0x18, .track = 1, .phase = RXWALK_NO_PHASE};
+        const qpp_result *ri = NULL;
+        const uint8_t *o = NULL;
+        if (f.launched) {
+            const uint32_t x = w->rix ? w->rix[i] : k++;
+            ri = &w->res[x];
+            o = w->hout + w->desc[x].out_off;
+            f.status = ri->status, f.hdr_len = ri->hdr_len, f.pn = ri->pn;
+            f.pn_off = w->desc[x].hdr_len, f.exp = w->desc[x].pn;
+            if (ri->status == QPP_S_OK) f.first = o[0];
+            if (w->phase) f.phase = w->phase[x];
         }
+        const RxWalkVerdict v = rxwalk_step(w->st, &f);
+        PyObject *di = PyLong_FromSsize_t(w->dg ? (Py_ssize_t)w->dg[i] : i);
+        if (!di) return -1;
+        PyObject *rec = NULL;
+        if (v == RXW_DEFERRED) {
+            /* the record's position, for the caller's general path */
+            PyObject *dj = w->dg ? PyLong_FromSsize_t(i) : di;
+            const int bad = dj ? PyList_Append(w->deferred, dj) : -1;
+            if (w->dg) Py_XDECREF(dj);
+            Py_DECREF(di);
+            if (bad < 0) return -1;
+            Py_INCREF(Py_None);
+            PyList_SetItem(w->recs, i, Py_None);
+            continue;
+        }
+        if (v == RXW_CLOSED) rec = drop_record(w, di, Py_None, g_s_closed);
+        else if (v == RXW_NO_KEY) rec = drop_record(w, di, w->epoch, g_s_key);
+        else if (v == RXW_RESERVED) rec = drop_record(w, di, w->epoch, g_s_rsv);
+        else if (v == RXW_FAILED) rec = drop_record(w, di, w->epoch, g_s_dec);
+        else {
+            const size_t pll = (size_t)ri->out_len - ri->hdr_len;
+            PyObject *h = PyBytes_FromStringAndSize(NULL, ri->hdr_len);
+            PyObject *pl = PyBytes_FromStringAndSize(NULL, (Py_ssize_t)pll);
+            PyObject *pn = PyLong_FromUnsignedLongLong(ri->pn);
+            if (h && pl && pn) {
+                w->od[w->on] = (uint8_t *)PyBytes_AsString(h), w->os_[w->on] = o, w->ol[w->on++] = ri->hdr_len;
+                w->od[w->on] = (uint8_t *)PyBytes_AsString(pl), w->os_[w->on] = o + ri->hdr_len, w->ol[w->on++] = pll;
+                w->otot += ri->hdr_len + pll;
+                PyObject *g[9] = {di, g_zero, Py_None, w->ptype, w->epoch, h, pl, pn, Py_None};
+                rec = make_record(w->tp, w->alloc, g, 9);
+            }
+            Py_XDECREF(h);
+            Py_XDECREF(pl);
+            Py_XDECREF(pn);
+        }
+        Py_DECREF(di);
+        if (!rec) return -1;
+        PyList_SetItem(w->recs, i, rec);
     }
-    rc = 0;
-done:
-    w->on = on;
-    w->otot = otot;
-    return rc;
+    return 0;
 }
 
 /* receive_short(table, items, conns, conn_cid_u32, conn_pair_u32,
@@ -2356,37 +2212,23 @@ static PyObject *py_receive_short(PyObject *m, PyObject *args)
     if (!items) return NULL;
 
     PtrMap pm = {0};
-    uint32_t *conn_of = NULL, *slot_of = NULL;
-    qpp_desc *desc = NULL;
-    uint8_t **cd = NULL;
-    const uint8_t **cs = NULL;
-    size_t *cl = NULL;
-    uint8_t *blocked_pair = NULL, *blocked_space = NULL, *blocked_conn = NULL;
-    PyObject *ret = NULL, *recs = NULL, *res = NULL, *deferred = NULL, *sexp_out = NULL, *closed_out = NULL;
-    PyObject *empty = NULL, *minus1 = NULL, *zero = NULL, *s_key = NULL, *s_dec = NULL, *s_rsv = NULL, *s_closed = NULL;
-    uint8_t **od = NULL;
-    const uint8_t **os_ = NULL;
-    size_t *ol = NULL, on = 0, otot = 0;
+    Scratch sc = {{NULL}, 0, 0};
+    WalkState ws = {.sexp = NULL, .closed = NULL};
+    PyObject *ret = NULL, *recs = NULL, *res = NULL, *deferred = NULL;
     int ins;
     if (ptrmap_init(&pm, (size_t)nc) < 0) goto nomem;
     for (Py_ssize_t c = 0; c < nc; ++c) (void)ptrmap_get(&pm, PyList_GetItem(conns, c), (uint32_t)c, &ins);
-    conn_of = (uint32_t *)malloc((n ? (size_t)n : 1) * sizeof(uint32_t));
-    slot_of = (uint32_t *)malloc((n ? (size_t)n : 1) * sizeof(uint32_t));
-    desc = (qpp_desc *)calloc(n ? (size_t)n : 1, sizeof(qpp_desc));
-    cd = (uint8_t **)malloc((n ? (size_t)n : 1) * sizeof(uint8_t *));
-    cs = (const uint8_t **)malloc((n ? (size_t)n : 1) * sizeof(uint8_t *));
-    cl = (size_t *)malloc((n ? (size_t)n : 1) * sizeof(size_t));
-    blocked_pair = (uint8_t *)calloc(n_pairs ? (size_t)n_pairs : 1, 1);
-    blocked_space = (uint8_t *)calloc(n_spaces ? (size_t)n_spaces : 1, 1);
-    blocked_conn = (uint8_t *)calloc(nc ? (size_t)nc : 1, 1);
+    uint32_t *conn_of = SCRATCH(&sc, uint32_t, n), *slot_of = SCRATCH(&sc, uint32_t, n);
+    qpp_desc *desc = SCRATCH0(&sc, qpp_desc, n);
+    uint8_t **cd = SCRATCH(&sc, uint8_t *, n);
+    const uint8_t **cs = SCRATCH(&sc, const uint8_t *, n);
+    size_t *cl = SCRATCH(&sc, size_t, n);
     /* output copies: header and payload of every packet, filled after the
        walk without the GIL (the bytes objects are not shared until returned) */
-    od = (uint8_t **)malloc((2 * (size_t)n + 1) * sizeof(uint8_t *));
-    os_ = (const uint8_t **)malloc((2 * (size_t)n + 1) * sizeof(uint8_t *));
-    ol = (size_t *)malloc((2 * (size_t)n + 1) * sizeof(size_t));
-    if (!conn_of || !slot_of || !desc || !cd || !cs || !cl || !blocked_pair || !blocked_space || !blocked_conn || !od ||
-        !os_ || !ol)
-        goto nomem;
+    uint8_t **od = SCRATCH(&sc, uint8_t *, 2 * n + 1);
+    const uint8_t **os_ = SCRATCH(&sc, const uint8_t *, 2 * n + 1);
+    size_t *ol = SCRATCH(&sc, size_t, 2 * n + 1);
+    if (sc.failed) goto nomem;
     /* classify: every datagram a short header long enough for its CID */
     size_t total = 0;
     uint32_t nl = 0;  /* packets to launch */
@@ -2415,21 +2257,11 @@ static PyObject *py_receive_short(PyObject *m, PyObject *args)
         total += (size_t)len;
         ++nl;
     }
+    if (walk_state_init(&ws, &sc, a_sexp, l_sexp, a_closed, l_closed, (size_t)n_pairs) < 0) goto done;
     res = PyBytes_FromStringAndSize(NULL, (Py_ssize_t)nl * (Py_ssize_t)sizeof(qpp_result));
-    sexp_out = PyBytes_FromStringAndSize(a_sexp, l_sexp);
-    closed_out = PyBytes_FromStringAndSize(a_closed, l_closed);
     recs = PyList_New(n);
     deferred = PyList_New(0);
-    empty = PyBytes_FromStringAndSize("", 0);
-    minus1 = PyLong_FromLong(-1);
-    zero = PyLong_FromLong(0);
-    s_key = PyUnicode_FromString("key_unavailable");
-    s_dec = PyUnicode_FromString("payload_decrypt_error");
-    s_rsv = PyUnicode_FromString("reserved_bits");
-    s_closed = PyUnicode_FromString("connection_closed");
-    if (!res || !sexp_out || !closed_out || !recs || !deferred || !empty || !minus1 || !zero || !s_key || !s_dec ||
-        !s_rsv || !s_closed)
-        goto nomem;
+    if (!res || !recs || !deferred) goto nomem;
     uint8_t *hin = NULL, *hout = NULL;
     if (nl) {
         qpp_session *ss = session();
@@ -2442,17 +2274,13 @@ static PyObject *py_receive_short(PyObject *m, PyObject *args)
     }
     {
         ShortWalk w = {n, NULL, NULL, conn_of, slot_of, cpair, cspace, desc, (const qpp_result *)PyBytes_AsString(res),
-                       hout, (uint64_t *)PyBytes_AsString(sexp_out), (uint8_t *)PyBytes_AsString(closed_out),
-                       blocked_pair, blocked_space, blocked_conn, recs, deferred, tp, alloc, ptype, epoch, empty,
-                       minus1, zero, s_key, s_dec, s_rsv, s_closed, od, os_, ol, 0, 0};
+                       hout, &ws.st, NULL, recs, deferred, tp, alloc, ptype, epoch, od, os_, ol, 0, 0};
         if (short_walk(&w) < 0) goto done;
-        on = w.on;
-        otot = w.otot;
+        Py_BEGIN_ALLOW_THREADS
+        par_copy(od, os_, ol, w.on, w.otot);
+        Py_END_ALLOW_THREADS
     }
-    Py_BEGIN_ALLOW_THREADS
-    par_copy(od, os_, ol, on, otot);
-    Py_END_ALLOW_THREADS
-    ret = PyTuple_Pack(4, recs, deferred, sexp_out, closed_out);
+    ret = PyTuple_Pack(4, recs, deferred, ws.sexp, ws.closed);
     goto done;
 fallback:
     Py_INCREF(Py_None);
@@ -2462,21 +2290,12 @@ nomem:
     PyErr_NoMemory();
 done:
     ptrmap_free(&pm);
-    free(conn_of), free(slot_of), free(desc), free(cd), free(cs), free(cl), free(blocked_pair), free(blocked_space);
-    free(blocked_conn), free(od), free(os_), free(ol);
+    scratch_free_all(&sc);
+    walk_state_clear(&ws);
     Py_DECREF(items);
-    Py_XDECREF(closed_out);
-    Py_XDECREF(s_rsv);
-    Py_XDECREF(s_closed);
-    Py_XDECREF(zero);
     Py_XDECREF(recs);
     Py_XDECREF(res);
     Py_XDECREF(deferred);
-    Py_XDECREF(sexp_out);
-    Py_XDECREF(empty);
-    Py_XDECREF(minus1);
-    Py_XDECREF(s_key);
-    Py_XDECREF(s_dec);
     return ret;
 }
 
@@ -2545,251 +2364,273 @@ done:
  * as a QPP_S_KEY_PHASE packet is.  pair_rolled has one byte per pair_slot
  * entry: the pairs whose keys the caller must now update.  The walk's arrays
  * may be empty when no datagram starts with a long header. */
-static PyObject *receive_routed_impl(PyObject *args, int mode)
-{
-    const int reply = mode == 3, accept = mode == 1 || reply, phased = mode == 2;
+typedef struct {
+    /* the 15 arguments every form takes */
     PyObject *t, *mo, *dgs, *rec_type, *ptype, *epoch;
-    const char *a_pair, *a_space, *a_pslot, *a_sexp, *a_closed, *a_kslot, *a_kexp, *a_arow = NULL, *a_aslot = NULL;
-    const char *a_pnext = NULL;
-    Py_ssize_t l_pair, l_space, l_pslot, l_sexp, l_closed, l_kslot, l_kexp, l_arow = 0, l_aslot = 0, l_pnext = 0;
-    unsigned int cid_len, accept_flags = 0, reply_flags = 0;
-    unsigned long long token_ctr = 0;
-    PyObject *rt = NULL;
-    const char *a_addr = NULL, *a_rand = NULL, *a_vers = NULL;
-    Py_ssize_t l_addr = 0, l_rand = 0, l_vers = 0;
+    const char *a_pair, *a_space, *a_pslot, *a_sexp, *a_kslot, *a_kexp, *a_closed;
+    Py_ssize_t l_pair, l_space, l_pslot, l_sexp, l_kslot, l_kexp, l_closed;
+    unsigned int cid_len;
     int walk;
-    if (!(reply ? PyArg_ParseTuple(args, "OOIO!y#y#y#y#y#y#OOOy#iy#y#IOy#y#Ky#I", &t, &mo, &cid_len, &PyList_Type, &dgs,
-                                   &a_pair, &l_pair, &a_space, &l_space, &a_pslot, &l_pslot, &a_sexp, &l_sexp, &a_kslot,
-                                   &l_kslot, &a_kexp, &l_kexp, &rec_type, &ptype, &epoch, &a_closed, &l_closed, &walk,
-                                   &a_arow, &l_arow, &a_aslot, &l_aslot, &accept_flags, &rt, &a_addr, &l_addr, &a_rand,
-                                   &l_rand, &token_ctr, &a_vers, &l_vers, &reply_flags)
-          : accept ? PyArg_ParseTuple(args, "OOIO!y#y#y#y#y#y#OOOy#iy#y#I", &t, &mo, &cid_len, &PyList_Type, &dgs, &a_pair,
-                                    &l_pair, &a_space, &l_space, &a_pslot, &l_pslot, &a_sexp, &l_sexp, &a_kslot,
-                                    &l_kslot, &a_kexp, &l_kexp, &rec_type, &ptype, &epoch, &a_closed, &l_closed, &walk,
-                                    &a_arow, &l_arow, &a_aslot, &l_aslot, &accept_flags)
-          : phased ? PyArg_ParseTuple(args, "OOIO!y#y#y#y#y#y#OOOy#iy#", &t, &mo, &cid_len, &PyList_Type, &dgs, &a_pair,
-                                      &l_pair, &a_space, &l_space, &a_pslot, &l_pslot, &a_sexp, &l_sexp, &a_kslot,
-                                      &l_kslot, &a_kexp, &l_kexp, &rec_type, &ptype, &epoch, &a_closed, &l_closed,
-                                      &walk, &a_pnext, &l_pnext)
-                 : PyArg_ParseTuple(args, "OOIO!y#y#y#y#y#y#OOOy#i", &t, &mo, &cid_len, &PyList_Type, &dgs, &a_pair,
-                                    &l_pair, &a_space, &l_space, &a_pslot, &l_pslot, &a_sexp, &l_sexp, &a_kslot,
-                                    &l_kslot, &a_kexp, &l_kexp, &rec_type, &ptype, &epoch, &a_closed, &l_closed,
-                                    &walk)))
-        return NULL;
-    qpp_keytab *kt = as_table(t);
-    qpp_cidmap *map = kt ? as_cidmap(mo) : NULL;
-    if (!map) return NULL;
-    qpp_keytab *reply_kt = reply ? as_table(rt) : NULL;
-    if (reply && !reply_kt) return NULL;
-    if (!PyType_Check(rec_type) || !PyType_IsSubtype((PyTypeObject *)rec_type, &PyTuple_Type)) {
+    /* the forms' tails: which were given, and what they hold */
+    int phased, accept, reply;
+    PyObject *rt;
+    const char *a_pnext, *a_arow, *a_aslot, *a_addr, *a_rand, *a_vers;
+    Py_ssize_t l_pnext, l_arow, l_aslot, l_addr, l_rand, l_vers;
+    unsigned int accept_flags, reply_flags;
+    unsigned long long token_ctr;
+    /* routed_prepare: what the arguments name, sizes, the per-connection arrays */
+    qpp_keytab *kt, *reply_kt;
+    qpp_cidmap *map;
+    PyTypeObject *tp;
+    allocfunc alloc;
+    PyObject *snap;  /* a snapshot holding a reference to every datagram: the copies run without the GIL */
+    Py_ssize_t n, nc, n_pairs, na;
+    int can_walk;
+    const uint32_t *cpair, *cspace;
+    uint32_t *cslot, *cnext;
+    uint64_t *cexp;
+    const uint32_t *kslot;  /* the walk form's arrays: the caller's, or, phased and given none, built here */
+    const uint64_t *kexp;
+    /* routed_launch: the staged batch and everything the device wrote */
+    uint32_t *lidx, nl;  /* datagrams whose first byte says long header: the device walks them */
+    size_t nd, total;
+    qpp_desc *desc;
+    qpp_result *res;
+    qpp_walk_rec *wrec;
+    uint32_t *wn;
+    uint8_t *phase, *hout;
+    PyObject *route, *acc, *km, *secrets, *rbuf, *rrec;
+    Scratch sc;
+} Routed;
+
+/* PyArg_ParseTuple over args[lo:hi] (what "y#" yields belongs to args' items, not to the slice) */
+static int parse_slice(PyObject *args, Py_ssize_t lo, Py_ssize_t hi, const char *fmt, ...)
+{
+    PyObject *part = PyTuple_GetSlice(args, lo, hi);
+    if (!part) return 0;
+    va_list va;
+    va_start(va, fmt);
+    const int ok = PyArg_VaParse(part, fmt, va);
+    va_end(va);
+    Py_DECREF(part);
+    return ok;
+}
+
+/* Checks, in the order the errors have always come, and the per-connection arrays. */
+static int routed_prepare(Routed *r)
+{
+    r->kt = as_table(r->t);
+    r->map = r->kt ? as_cidmap(r->mo) : NULL;
+    if (!r->map) return -1;
+    r->reply_kt = r->reply ? as_table(r->rt) : NULL;
+    if (r->reply && !r->reply_kt) return -1;
+    if (!PyType_Check(r->rec_type) || !PyType_IsSubtype((PyTypeObject *)r->rec_type, &PyTuple_Type)) {
         PyErr_SetString(PyExc_TypeError, "rec_type must be a tuple subclass");
-        return NULL;
+        return -1;
     }
-    if (cid_len < 1 || cid_len > QPP_CID_MAX) {
+    if (r->cid_len < 1 || r->cid_len > QPP_CID_MAX) {
         PyErr_SetString(PyExc_ValueError, "cid_len must be 1..20");
-        return NULL;
+        return -1;
     }
-    const Py_ssize_t n = PyList_Size(dgs), nc = l_closed;
-    const Py_ssize_t n_pairs = l_pslot / 4, n_spaces = l_sexp / 8;
-    if (check_len(l_pair, nc, 4, "conn_pair") < 0 || check_len(l_space, nc, 4, "conn_space") < 0) return NULL;
+    const Py_ssize_t n = PyList_Size(r->dgs), nc = r->l_closed, n_pairs = r->l_pslot / 4, n_spaces = r->l_sexp / 8;
+    r->n = n, r->nc = nc, r->n_pairs = n_pairs;
+    if (check_len(r->l_pair, nc, 4, "conn_pair") < 0 || check_len(r->l_space, nc, 4, "conn_space") < 0) return -1;
     /* the walk's per-key-set and per-space arrays: both or neither */
-    const int can_walk = l_kslot || l_kexp || nc == 0;
-    if (can_walk && (check_len(l_kslot, nc, 4 * QPP_KEYSETS, "conn_keyset_slot") < 0 ||
-                     check_len(l_kexp, nc, 8 * QPP_SPACES, "conn_space_exp") < 0))
-        return NULL;
-    const uint32_t *cpair = (const uint32_t *)a_pair, *cspace = (const uint32_t *)a_space,
-                   *pslot = (const uint32_t *)a_pslot;
+    const int given = r->l_kslot || r->l_kexp;
+    r->can_walk = given || nc == 0;
+    if (r->can_walk && (check_len(r->l_kslot, nc, 4 * QPP_KEYSETS, "conn_keyset_slot") < 0 ||
+                        check_len(r->l_kexp, nc, 8 * QPP_SPACES, "conn_space_exp") < 0))
+        return -1;
+    const uint32_t *cpair = r->cpair = (const uint32_t *)r->a_pair, *cspace = r->cspace = (const uint32_t *)r->a_space;
     for (Py_ssize_t c = 0; c < nc; ++c)
         if ((Py_ssize_t)cpair[c] >= n_pairs || (Py_ssize_t)cspace[c] >= n_spaces) {
             PyErr_SetString(PyExc_ValueError, "pair or space index out of range");
-            return NULL;
+            return -1;
         }
     if (n > 0x7fffffff || nc > 0x7fffffff) {
         PyErr_SetString(PyExc_ValueError, "batch too large");
-        return NULL;
+        return -1;
     }
-    if (phased && l_pnext != l_pslot) {
+    if (r->phased && r->l_pnext != r->l_pslot) {
         PyErr_SetString(PyExc_ValueError, "pair_next: one u32 per pair_slot entry");
-        return NULL;
+        return -1;
     }
-    const Py_ssize_t na = l_arow / 4;
-    if (accept && (l_arow % 4 || l_aslot != 8 * na || na > n || !walk || !(l_kslot || l_kexp || nc == 0))) {
+    r->na = r->l_arow / 4;
+    if (r->accept && (r->l_arow % 4 || r->l_aslot != 8 * r->na || r->na > n || !r->walk || !r->can_walk)) {
         PyErr_SetString(PyExc_ValueError, "acc_row: whole u32 items, no more than datagrams; acc_slot: two u32 each; "
                                           "the walk's arrays are required");
-        return NULL;
+        return -1;
     }
-    if (reply && ((l_addr && l_addr != QPP_RP_ADDR_STRIDE * na) || l_rand != QPP_RP_RAND_STRIDE * na || l_vers % 4)) {
+    if (r->reply && ((r->l_addr && r->l_addr != QPP_RP_ADDR_STRIDE * r->na) ||
+                     r->l_rand != QPP_RP_RAND_STRIDE * r->na || r->l_vers % 4)) {
         PyErr_SetString(PyExc_ValueError, "addr: 20 bytes per candidate or none; rand: 16 bytes per candidate; "
                                           "versions: whole u32 items");
-        return NULL;
+        return -1;
     }
-    PyTypeObject *tp = (PyTypeObject *)rec_type;
-    allocfunc alloc = (allocfunc)PyType_GetSlot(tp, Py_tp_alloc);
-    if (!alloc) return NULL;
-    /* a snapshot holding a reference to every datagram: the copies below run without the GIL */
-    dgs = PySequence_Tuple(dgs);
-    if (!dgs) return NULL;
-
-    const size_t n1 = n ? (size_t)n : 1, nc1 = nc ? (size_t)nc : 1;
-    uint64_t *offs = (uint64_t *)malloc(n1 * sizeof(uint64_t)), *cexp = (uint64_t *)malloc(nc1 * sizeof(uint64_t));
-    uint32_t *lens = (uint32_t *)malloc(n1 * sizeof(uint32_t)), *cslot = (uint32_t *)malloc(nc1 * sizeof(uint32_t));
-    uint32_t *conn_of = (uint32_t *)malloc(n1 * sizeof(uint32_t)), *slot_of = (uint32_t *)malloc(n1 * sizeof(uint32_t));
-    uint32_t *dg = (uint32_t *)malloc(n1 * sizeof(uint32_t)), *lidx = (uint32_t *)malloc(n1 * sizeof(uint32_t));
-    qpp_desc *desc = NULL;
-    qpp_result *res = NULL;
-    qpp_walk_rec *wrec = NULL;
-    uint32_t *wn = NULL;
-    uint8_t **cd = (uint8_t **)malloc(n1 * sizeof(uint8_t *));
-    const uint8_t **cs = (const uint8_t **)malloc(n1 * sizeof(uint8_t *));
-    size_t *cl = (size_t *)malloc(n1 * sizeof(size_t));
-    uint8_t *blocked_pair = (uint8_t *)calloc(n_pairs ? (size_t)n_pairs : 1, 1);
-    uint8_t *blocked_space = (uint8_t *)calloc(n_spaces ? (size_t)n_spaces : 1, 1);
-    uint8_t *blocked_conn = (uint8_t *)calloc(nc1, 1);
-    uint8_t **od = (uint8_t **)malloc((2 * (size_t)n + 1) * sizeof(uint8_t *));
-    const uint8_t **os_ = (const uint8_t **)malloc((2 * (size_t)n + 1) * sizeof(uint8_t *));
-    size_t *ol = (size_t *)malloc((2 * (size_t)n + 1) * sizeof(size_t));
-    PyObject *ret = NULL, *route = NULL, *recs = NULL, *deferred = NULL, *sexp_out = NULL, *closed_out = NULL;
-    PyObject *empty = NULL, *minus1 = NULL, *zero = NULL, *s_key = NULL, *s_dec = NULL, *s_rsv = NULL, *s_closed = NULL;
-    PyObject *walked = NULL, *longs = NULL, *acc = NULL, *km = NULL, *secrets = NULL, *rolled_out = NULL;
-    PyObject *rbuf = NULL, *rrec = NULL;
-    /* phased: the per-connection next-phase slots, the device's verdicts, and the walk form's arrays when
-       the caller gave none (a batch with no long header) */
-    uint32_t *cnext = NULL, *ks_own = NULL;
+    r->tp = (PyTypeObject *)r->rec_type;
+    r->alloc = (allocfunc)PyType_GetSlot(r->tp, Py_tp_alloc);
+    if (!r->alloc) return -1;
+    r->snap = PySequence_Tuple(r->dgs);
+    if (!r->snap) return -1;
+    /* what the routing kernel hands a connection's datagrams: a closed or keyless one gets no slot */
+    const uint8_t *closed = (const uint8_t *)r->a_closed;
+    r->cslot = SCRATCH(&r->sc, uint32_t, nc);
+    r->cexp = SCRATCH(&r->sc, uint64_t, nc);
+    r->kslot = (const uint32_t *)r->a_kslot, r->kexp = (const uint64_t *)r->a_kexp;
+    uint32_t *ks_own = NULL;
     uint64_t *ke_own = NULL;
-    uint8_t *phase = NULL;
-    if (phased) {
-        cnext = (uint32_t *)malloc(nc1 * sizeof(uint32_t));
-        phase = (uint8_t *)calloc(n1, 1);
-        if (!cnext || !phase) goto nomem;
-        if (!(l_kslot || l_kexp)) {
-            ks_own = (uint32_t *)malloc(nc1 * QPP_KEYSETS * sizeof(uint32_t));
-            ke_own = (uint64_t *)calloc(nc1 * QPP_SPACES, sizeof(uint64_t));
-            if (!ks_own || !ke_own) goto nomem;
+    if (r->phased) {
+        /* the next-phase slots, and the walk form's arrays when the caller gave none (no long header) */
+        r->cnext = SCRATCH(&r->sc, uint32_t, nc);
+        if (!given) {
+            r->kslot = ks_own = SCRATCH(&r->sc, uint32_t, nc * QPP_KEYSETS);
+            r->kexp = ke_own = SCRATCH0(&r->sc, uint64_t, nc * QPP_SPACES);
         }
     }
-    if (accept) {
-        acc = PyBytes_FromStringAndSize(NULL, na * (Py_ssize_t)sizeof(qpp_accept_rec));
-        km = PyBytes_FromStringAndSize(NULL, na * 2 * (Py_ssize_t)sizeof(qpp_key_material));
-        secrets = PyBytes_FromStringAndSize(NULL, na * 64);
-        if (!acc || !km || !secrets) goto nomem;
+    if (r->sc.failed) return PyErr_NoMemory(), -1;
+    for (Py_ssize_t c = 0; c < nc; ++c) {
+        r->cslot[c] = closed[c] ? QPP_SLOT_NONE : ((const uint32_t *)r->a_pslot)[cpair[c]];
+        r->cexp[c] = ((const uint64_t *)r->a_sexp)[cspace[c]];
+        if (r->cnext) r->cnext[c] = closed[c] ? QPP_SLOT_NONE : ((const uint32_t *)r->a_pnext)[cpair[c]];
+        if (ks_own) {
+            for (int j = 0; j < QPP_KEYSETS - 1; ++j) ks_own[c * QPP_KEYSETS + j] = QPP_SLOT_NONE;
+            ks_own[c * QPP_KEYSETS + QPP_KEYSETS - 1] = r->cslot[c];
+            ke_own[c * QPP_SPACES + QPP_SPACES - 1] = r->cexp[c];
+        }
     }
-    if (reply) {
+    return 0;
+}
+
+/* Stage the datagrams, list the long headers, run the form's one session call. */
+static int routed_launch(Routed *r)
+{
+    const Py_ssize_t n = r->n, na = r->na;
+    Scratch *sc = &r->sc;
+    uint64_t *offs = SCRATCH(sc, uint64_t, n);
+    uint32_t *lens = SCRATCH(sc, uint32_t, n);
+    uint8_t **cd = SCRATCH(sc, uint8_t *, n);
+    const uint8_t **cs = SCRATCH(sc, const uint8_t *, n);
+    size_t *cl = SCRATCH(sc, size_t, n);
+    r->lidx = SCRATCH(sc, uint32_t, n);
+    if (r->phased) r->phase = SCRATCH0(sc, uint8_t, n);
+    if (sc->failed) return PyErr_NoMemory(), -1;
+    if (r->accept) {
+        r->acc = PyBytes_FromStringAndSize(NULL, na * (Py_ssize_t)sizeof(qpp_accept_rec));
+        r->km = PyBytes_FromStringAndSize(NULL, na * 2 * (Py_ssize_t)sizeof(qpp_key_material));
+        r->secrets = PyBytes_FromStringAndSize(NULL, na * 64);
+        if (!r->acc || !r->km || !r->secrets) return -1;
+    }
+    if (r->reply) {
         /* zeros when the call makes no reply (no flag, no candidate) */
-        rbuf = PyBytes_FromStringAndSize(NULL, na * QPP_REPLY_STRIDE);
-        rrec = PyBytes_FromStringAndSize(NULL, na * (Py_ssize_t)sizeof(qpp_reply_rec));
-        if (!rbuf || !rrec) goto nomem;
-        memset(PyBytes_AsString(rbuf), 0, (size_t)na * QPP_REPLY_STRIDE);
-        memset(PyBytes_AsString(rrec), 0, (size_t)na * sizeof(qpp_reply_rec));
+        r->rbuf = PyBytes_FromStringAndSize(NULL, na * QPP_REPLY_STRIDE);
+        r->rrec = PyBytes_FromStringAndSize(NULL, na * (Py_ssize_t)sizeof(qpp_reply_rec));
+        if (!r->rbuf || !r->rrec) return -1;
+        memset(PyBytes_AsString(r->rbuf), 0, (size_t)na * QPP_REPLY_STRIDE);
+        memset(PyBytes_AsString(r->rrec), 0, (size_t)na * sizeof(qpp_reply_rec));
     }
-    if (!offs || !cexp || !lens || !cslot || !conn_of || !slot_of || !dg || !lidx || !cd || !cs || !cl ||
-        !blocked_pair || !blocked_space || !blocked_conn || !od || !os_ || !ol)
-        goto nomem;
     size_t total = 0;
-    uint32_t nl = 0;  /* datagrams whose first byte says long header: the device walks them */
+    uint32_t nl = 0;
     for (Py_ssize_t i = 0; i < n; ++i) {
-        PyObject *d = PyTuple_GetItem(dgs, i);
+        PyObject *d = PyTuple_GetItem(r->snap, i);
         if (!d || !PyBytes_Check(d)) {
             PyErr_SetString(PyExc_TypeError, "datagrams must be bytes");
-            goto done;
+            return -1;
         }
         const Py_ssize_t len = PyBytes_Size(d);
         if ((uint64_t)len > 0xffffffffu) {
             PyErr_SetString(PyExc_ValueError, "datagram too long");
-            goto done;
+            return -1;
         }
         offs[i] = total;
         lens[i] = (uint32_t)len;
         cs[i] = (const uint8_t *)PyBytes_AsString(d);
         cl[i] = (size_t)len;
         total += (size_t)len;
-        if (walk && can_walk && len && (cs[i][0] & 0x80)) lidx[nl++] = (uint32_t)i;
+        if (r->walk && r->can_walk && len && (cs[i][0] & 0x80)) r->lidx[nl++] = (uint32_t)i;
     }
     if ((uint64_t)n + 3ull * nl > 0x7fffffffull) nl = 0;  /* past the fused call's limit: the general path */
-    if (accept && na && !nl) {
+    if (r->accept && na && !nl) {
         PyErr_SetString(PyExc_ValueError, "candidates without a listed long-header datagram");
-        goto done;
+        return -1;
     }
-    const size_t nd = (size_t)n + 3 * (size_t)nl, nd1 = nd ? nd : 1, nl1 = nl ? nl : 1;
-    desc = (qpp_desc *)malloc(nd1 * sizeof(qpp_desc));
-    res = (qpp_result *)malloc(nd1 * sizeof(qpp_result));
-    wrec = (qpp_walk_rec *)calloc(nl1 * QPP_WALK_MAX, sizeof(qpp_walk_rec));
-    wn = (uint32_t *)calloc(nl1, sizeof(uint32_t));
-    if (!desc || !res || !wrec || !wn) goto nomem;
-    for (Py_ssize_t c = 0; c < nc; ++c) {
-        cslot[c] = ((const uint8_t *)a_closed)[c] ? QPP_SLOT_NONE : pslot[cpair[c]];
-        cexp[c] = ((const uint64_t *)a_sexp)[cspace[c]];
-        if (phased) {
-            cnext[c] = ((const uint8_t *)a_closed)[c] ? QPP_SLOT_NONE : ((const uint32_t *)a_pnext)[cpair[c]];
-            if (ks_own) {
-                for (int j = 0; j < QPP_KEYSETS - 1; ++j) ks_own[c * QPP_KEYSETS + j] = QPP_SLOT_NONE;
-                ks_own[c * QPP_KEYSETS + QPP_KEYSETS - 1] = cslot[c];
-                ke_own[c * QPP_SPACES + QPP_SPACES - 1] = cexp[c];
-            }
-        }
+    const size_t nd = (size_t)n + 3 * (size_t)nl;
+    r->nl = nl, r->nd = nd, r->total = total;
+    r->desc = SCRATCH(sc, qpp_desc, nd);
+    r->res = SCRATCH(sc, qpp_result, nd);
+    r->wrec = SCRATCH0(sc, qpp_walk_rec, (size_t)(nl ? nl : 1) * QPP_WALK_MAX);
+    r->wn = SCRATCH0(sc, uint32_t, nl);
+    if (sc->failed) return PyErr_NoMemory(), -1;
+    r->route = PyBytes_FromStringAndSize(NULL, n * (Py_ssize_t)sizeof(qpp_route_rec));
+    if (!r->route) return -1;
+    if (!n) return 0;
+    qpp_route_rec *rr = (qpp_route_rec *)PyBytes_AsString(r->route);
+    qpp_session *ss = session();
+    uint8_t *hin = NULL;
+    if (!ss || check_rc(qpp_session_stage(ss, total ? total : 1, (uint32_t)nd, &hin, &r->hout)) < 0) return -1;
+    for (Py_ssize_t i = 0; i < n; ++i) cd[i] = hin + offs[i];
+    const char *refused = NULL;
+    int rc;
+    Py_BEGIN_ALLOW_THREADS  /* the snapshot holds every datagram */
+    par_copy(cd, cs, cl, (size_t)n, total);
+    if (r->reply) {
+        refused = "bad accept or reply arguments (those of receive_accept, a reply table of fewer than 3 slots, an "
+                  "address length that is neither 6 nor 18, not 1..16 versions, an unknown reply flag, or a token "
+                  "counter that wraps); nothing was launched";
+        rc = qpp_session_accept_reply_unprotect(
+            ss, r->kt, r->map, r->cid_len, offs, lens, (uint32_t)n, hin, total, r->lidx, nl, r->kslot, r->kexp,
+            (uint32_t)r->nc, 0, (const uint32_t *)r->a_arow, (const uint32_t *)r->a_aslot, (uint32_t)na,
+            r->accept_flags, r->reply_kt, r->l_addr ? (const uint8_t *)r->a_addr : NULL, (const uint8_t *)r->a_rand,
+            r->token_ctr, (const uint32_t *)r->a_vers, (uint32_t)(r->l_vers / 4), r->reply_flags, r->hout, total,
+            r->desc, rr, r->res, r->wrec, r->wn, (qpp_accept_rec *)PyBytes_AsString(r->acc),
+            (qpp_key_material *)PyBytes_AsString(r->km), (uint8_t *)PyBytes_AsString(r->secrets),
+            (uint8_t *)PyBytes_AsString(r->rbuf), (qpp_reply_rec *)PyBytes_AsString(r->rrec));
+    } else if (r->accept) {
+        refused = "bad accept arguments (acc_row not strictly increasing below the listed datagrams, a slot outside "
+                  "the table or named twice, or an unknown flag); nothing was launched";
+        rc = qpp_session_accept_unprotect(ss, r->kt, r->map, r->cid_len, offs, lens, (uint32_t)n, hin, total, r->lidx,
+                                          nl, r->kslot, r->kexp, (uint32_t)r->nc, 0, (const uint32_t *)r->a_arow,
+                                          (const uint32_t *)r->a_aslot, (uint32_t)na, r->accept_flags, r->hout, total,
+                                          r->desc, rr, r->res, r->wrec, r->wn,
+                                          (qpp_accept_rec *)PyBytes_AsString(r->acc),
+                                          (qpp_key_material *)PyBytes_AsString(r->km),
+                                          (uint8_t *)PyBytes_AsString(r->secrets));
+    } else if (r->phased) {
+        refused = "bad arguments (a next-phase slot outside the table); nothing was launched";
+        rc = qpp_session_route_phase_unprotect(ss, r->kt, r->map, r->cid_len, offs, lens, (uint32_t)n, hin, total,
+                                               r->lidx, nl, r->kslot, r->kexp, (uint32_t)r->nc, r->cnext, 0, r->hout,
+                                               total, r->desc, rr, r->res, r->wrec, r->wn, r->phase);
+    } else if (nl) {
+        rc = qpp_session_route_walk_unprotect(ss, r->kt, r->map, r->cid_len, offs, lens, (uint32_t)n, hin, total,
+                                              r->lidx, nl, r->kslot, r->kexp, (uint32_t)r->nc, 0, r->hout, total,
+                                              r->desc, rr, r->res, r->wrec, r->wn);
+    } else {
+        rc = qpp_session_route_unprotect(ss, r->kt, r->map, r->cid_len, offs, lens, (uint32_t)n, hin, total, r->cslot,
+                                         r->cexp, (uint32_t)r->nc, 0, r->hout, total, r->desc, rr, r->res);
     }
-    route = PyBytes_FromStringAndSize(NULL, n * (Py_ssize_t)sizeof(qpp_route_rec));
-    if (!route) goto done;
-    const qpp_route_rec *rr = (const qpp_route_rec *)PyBytes_AsString(route);
-    uint8_t *hin = NULL, *hout = NULL;
-    if (n) {
-        qpp_session *ss = session();
-        if (!ss || check_rc(qpp_session_stage(ss, total ? total : 1, (uint32_t)nd, &hin, &hout)) < 0) goto done;
-        for (Py_ssize_t i = 0; i < n; ++i) cd[i] = hin + offs[i];
-        int rc;
-        Py_BEGIN_ALLOW_THREADS  /* the snapshot holds every datagram */
-        par_copy(cd, cs, cl, (size_t)n, total);
-        if (reply)
-            rc = qpp_session_accept_reply_unprotect(
-                ss, kt, map, cid_len, offs, lens, (uint32_t)n, hin, total, lidx, nl, (const uint32_t *)a_kslot,
-                (const uint64_t *)a_kexp, (uint32_t)nc, 0, (const uint32_t *)a_arow, (const uint32_t *)a_aslot,
-                (uint32_t)na, accept_flags, reply_kt, l_addr ? (const uint8_t *)a_addr : NULL, (const uint8_t *)a_rand,
-                token_ctr, (const uint32_t *)a_vers, (uint32_t)(l_vers / 4), reply_flags, hout, total, desc,
-                (qpp_route_rec *)rr, res, wrec, wn, (qpp_accept_rec *)PyBytes_AsString(acc),
-                (qpp_key_material *)PyBytes_AsString(km), (uint8_t *)PyBytes_AsString(secrets),
-                (uint8_t *)PyBytes_AsString(rbuf), (qpp_reply_rec *)PyBytes_AsString(rrec));
-        else if (accept)
-            rc = qpp_session_accept_unprotect(ss, kt, map, cid_len, offs, lens, (uint32_t)n, hin, total, lidx, nl,
-                                              (const uint32_t *)a_kslot, (const uint64_t *)a_kexp, (uint32_t)nc, 0,
-                                              (const uint32_t *)a_arow, (const uint32_t *)a_aslot, (uint32_t)na,
-                                              accept_flags, hout, total, desc, (qpp_route_rec *)rr, res, wrec, wn,
-                                              (qpp_accept_rec *)PyBytes_AsString(acc),
-                                              (qpp_key_material *)PyBytes_AsString(km),
-                                              (uint8_t *)PyBytes_AsString(secrets));
-        else if (phased)
-            rc = qpp_session_route_phase_unprotect(ss, kt, map, cid_len, offs, lens, (uint32_t)n, hin, total, lidx, nl,
-                                                   ks_own ? ks_own : (const uint32_t *)a_kslot,
-                                                   ke_own ? ke_own : (const uint64_t *)a_kexp, (uint32_t)nc, cnext,
-                                                   0, hout, total, desc, (qpp_route_rec *)rr, res, wrec, wn, phase);
-        else if (nl)
-            rc = qpp_session_route_walk_unprotect(ss, kt, map, cid_len, offs, lens, (uint32_t)n, hin, total, lidx, nl,
-                                                  (const uint32_t *)a_kslot, (const uint64_t *)a_kexp, (uint32_t)nc,
-                                                  0, hout, total, desc, (qpp_route_rec *)rr, res, wrec, wn);
-        else
-            rc = qpp_session_route_unprotect(ss, kt, map, cid_len, offs, lens, (uint32_t)n, hin, total, cslot, cexp,
-                                             (uint32_t)nc, 0, hout, total, desc, (qpp_route_rec *)rr, res);
-        Py_END_ALLOW_THREADS
-        if (phased && rc == QPP_E_ARG) {
-            PyErr_SetString(PyExc_ValueError, "bad arguments (a next-phase slot outside the table); nothing was "
-                                              "launched");
-            goto done;
-        }
-        if (reply && rc == QPP_E_ARG) {
-            PyErr_SetString(PyExc_ValueError, "bad accept or reply arguments (those of receive_accept, a reply table "
-                                              "of fewer than 3 slots, an address length that is neither 6 nor 18, "
-                                              "not 1..16 versions, an unknown reply flag, or a token counter that "
-                                              "wraps); nothing was launched");
-            goto done;
-        }
-        if (accept && rc == QPP_E_ARG) {
-            PyErr_SetString(PyExc_ValueError, "bad accept arguments (acc_row not strictly increasing below the listed "
-                                              "datagrams, a slot outside the table or named twice, or an unknown "
-                                              "flag); nothing was launched");
-            goto done;
-        }
-        if (check_rc(rc) < 0) goto done;
+    Py_END_ALLOW_THREADS
+    if (rc == QPP_E_ARG && refused) {
+        PyErr_SetString(PyExc_ValueError, refused);
+        return -1;
     }
-    if (accept) walk = 0;  /* the in-order walk is the caller's */
-    /* the records to walk: the short-header datagrams of known connections */
+    return check_rc(rc);
+}
+
+/* The in-order walk over the short-header datagrams of known connections, or what the caller needs to
+ * run its own; then the form's result tuple. */
+static PyObject *routed_result(Routed *r)
+{
+    const Py_ssize_t n = r->n;
+    const qpp_route_rec *rr = (const qpp_route_rec *)PyBytes_AsString(r->route);
+    const uint8_t *closed = (const uint8_t *)r->a_closed;
+    PyObject *ret = NULL, *longs = NULL, *recs = NULL, *deferred = NULL, *rolled = NULL, *walked = NULL;
+    WalkState ws = {.sexp = NULL, .closed = NULL};
+    uint32_t *dg = SCRATCH(&r->sc, uint32_t, n), *conn_of = SCRATCH(&r->sc, uint32_t, n);
+    uint32_t *slot_of = SCRATCH(&r->sc, uint32_t, n);
+    uint8_t **od = SCRATCH(&r->sc, uint8_t *, 2 * n + 1);
+    const uint8_t **os_ = SCRATCH(&r->sc, const uint8_t *, 2 * n + 1);
+    size_t *ol = SCRATCH(&r->sc, size_t, 2 * n + 1);
+    if (r->sc.failed) return PyErr_NoMemory();
+    int walk = r->walk && !r->accept;  /* accepting: the in-order walk is the caller's */
     Py_ssize_t nr = 0;
     for (Py_ssize_t i = 0; i < n && walk; ++i) {
         if (rr[i].cls == QPP_R_LONG && rr[i].conn != QPP_CONN_NONE) walk = 0;
@@ -2797,105 +2638,98 @@ static PyObject *receive_routed_impl(PyObject *args, int mode)
         const uint32_t c = rr[i].conn;  /* < nc: the kernel checked it */
         dg[nr] = (uint32_t)i;
         conn_of[nr] = c;
-        slot_of[nr] = ((const uint8_t *)a_closed)[c] ? RS_CLOSED : cslot[c];
+        slot_of[nr] = closed[c] ? RS_CLOSED : r->cslot[c];
         ++nr;
     }
     if (!walk) {
         /* long headers of known connections: with the device's walk of them
            (walk records, every descriptor and result, the output), or for
            the caller's general path */
-        if (nl) {
-            PyObject *f[6] = {PyBytes_FromStringAndSize((const char *)lidx, (Py_ssize_t)nl * 4),
-                              PyBytes_FromStringAndSize((const char *)wrec,
-                                                        (Py_ssize_t)nl * QPP_WALK_MAX * (Py_ssize_t)sizeof(qpp_walk_rec)),
-                              PyBytes_FromStringAndSize((const char *)wn, (Py_ssize_t)nl * 4),
-                              PyBytes_FromStringAndSize((const char *)desc, (Py_ssize_t)(nd * sizeof(qpp_desc))),
-                              PyBytes_FromStringAndSize((const char *)res, (Py_ssize_t)(nd * sizeof(qpp_result))),
-                              PyBytes_FromStringAndSize((const char *)hout, (Py_ssize_t)total)};
+        if (r->nl) {
+            const Py_ssize_t nl = r->nl;
+            PyObject *f[6] = {PyBytes_FromStringAndSize((const char *)r->lidx, nl * 4),
+                              PyBytes_FromStringAndSize((const char *)r->wrec,
+                                                        nl * QPP_WALK_MAX * (Py_ssize_t)sizeof(qpp_walk_rec)),
+                              PyBytes_FromStringAndSize((const char *)r->wn, nl * 4),
+                              PyBytes_FromStringAndSize((const char *)r->desc, (Py_ssize_t)(r->nd * sizeof(qpp_desc))),
+                              PyBytes_FromStringAndSize((const char *)r->res, (Py_ssize_t)(r->nd * sizeof(qpp_result))),
+                              PyBytes_FromStringAndSize((const char *)r->hout, (Py_ssize_t)r->total)};
             if (f[0] && f[1] && f[2] && f[3] && f[4] && f[5]) longs = PyTuple_Pack(6, f[0], f[1], f[2], f[3], f[4], f[5]);
             for (int k = 0; k < 6; ++k) Py_XDECREF(f[k]);
-            if (!longs) goto done;
+            if (!longs) return NULL;
         }
-        if (accept) {
-            PyObject *found = PyTuple_Pack(3, acc, km, secrets);
-            PyObject *sent = reply && found ? PyTuple_Pack(2, rbuf, rrec) : NULL;
-            if (found && reply) {
-                if (sent) ret = PyTuple_Pack(5, route, Py_None, longs ? longs : Py_None, found, sent);
-            } else if (found) {
-                ret = PyTuple_Pack(4, route, Py_None, longs ? longs : Py_None, found);
-            }
-            Py_XDECREF(sent);
-            Py_XDECREF(found);
-        } else {
-            ret = PyTuple_Pack(3, route, Py_None, longs ? longs : Py_None);
-        }
-        goto done;
+        PyObject *found = r->accept ? PyTuple_Pack(3, r->acc, r->km, r->secrets) : NULL;
+        PyObject *sent = r->reply && found ? PyTuple_Pack(2, r->rbuf, r->rrec) : NULL;
+        if (sent) ret = PyTuple_Pack(5, r->route, Py_None, longs ? longs : Py_None, found, sent);
+        else if (found && !r->reply) ret = PyTuple_Pack(4, r->route, Py_None, longs ? longs : Py_None, found);
+        else if (!r->accept) ret = PyTuple_Pack(3, r->route, Py_None, longs ? longs : Py_None);
+        Py_XDECREF(sent);
+        Py_XDECREF(found);
+        Py_XDECREF(longs);
+        return ret;
     }
-    sexp_out = PyBytes_FromStringAndSize(a_sexp, l_sexp);
-    closed_out = PyBytes_FromStringAndSize(a_closed, l_closed);
     recs = PyList_New(nr);
     deferred = PyList_New(0);
-    empty = PyBytes_FromStringAndSize("", 0);
-    minus1 = PyLong_FromLong(-1);
-    zero = PyLong_FromLong(0);
-    s_key = PyUnicode_FromString("key_unavailable");
-    s_dec = PyUnicode_FromString("payload_decrypt_error");
-    s_rsv = PyUnicode_FromString("reserved_bits");
-    s_closed = PyUnicode_FromString("connection_closed");
-    if (phased) {
-        rolled_out = PyBytes_FromStringAndSize(NULL, n_pairs);
-        if (!rolled_out) goto nomem;
-        memset(PyBytes_AsString(rolled_out), 0, (size_t)n_pairs);
+    if (walk_state_init(&ws, &r->sc, r->a_sexp, r->l_sexp, r->a_closed, r->l_closed, (size_t)r->n_pairs) < 0) goto done;
+    if (r->phased) {
+        rolled = PyBytes_FromStringAndSize(NULL, r->n_pairs);
+        if (!rolled) goto done;
+        ws.st.rolled = (uint8_t *)memset(PyBytes_AsString(rolled), 0, (size_t)r->n_pairs);
     }
-    if (!sexp_out || !closed_out || !recs || !deferred || !empty || !minus1 || !zero || !s_key || !s_dec || !s_rsv ||
-        !s_closed)
-        goto nomem;
+    if (!recs || !deferred) goto done;
     {
-        ShortWalk w = {nr, dg, dg, conn_of, slot_of, cpair, cspace, desc, res,
-                       hout, (uint64_t *)PyBytes_AsString(sexp_out), (uint8_t *)PyBytes_AsString(closed_out),
-                       blocked_pair, blocked_space, blocked_conn, recs, deferred, tp, alloc, ptype, epoch, empty,
-                       minus1, zero, s_key, s_dec, s_rsv, s_closed, od, os_, ol, 0, 0, NULL, NULL};
-        if (phased) {
-            w.phase = phase;
-            w.rolled = (uint8_t *)PyBytes_AsString(rolled_out);
-        }
+        ShortWalk w = {nr, dg, dg, conn_of, slot_of, r->cpair, r->cspace, r->desc, r->res, r->hout, &ws.st, r->phase,
+                       recs, deferred, r->tp, r->alloc, r->ptype, r->epoch, od, os_, ol, 0, 0};
         if (short_walk(&w) < 0) goto done;
         Py_BEGIN_ALLOW_THREADS
         par_copy(od, os_, ol, w.on, w.otot);
         Py_END_ALLOW_THREADS
     }
-    walked = phased ? PyTuple_Pack(5, recs, deferred, sexp_out, closed_out, rolled_out)
-                    : PyTuple_Pack(4, recs, deferred, sexp_out, closed_out);
-    if (walked) ret = PyTuple_Pack(3, route, walked, Py_None);
-    goto done;
-nomem:
-    PyErr_NoMemory();
+    walked = rolled ? PyTuple_Pack(5, recs, deferred, ws.sexp, ws.closed, rolled)
+                    : PyTuple_Pack(4, recs, deferred, ws.sexp, ws.closed);
+    if (walked) ret = PyTuple_Pack(3, r->route, walked, Py_None);
 done:
-    free(offs), free(cexp), free(lens), free(cslot), free(conn_of), free(slot_of), free(dg), free(desc), free(res);
-    free(lidx), free(wrec), free(wn), free(cnext), free(phase), free(ks_own), free(ke_own);
-    Py_XDECREF(rolled_out);
-    Py_XDECREF(longs);
-    Py_XDECREF(acc);
-    Py_XDECREF(km);
-    Py_XDECREF(secrets);
-    Py_XDECREF(rbuf);
-    Py_XDECREF(rrec);
-    free(cd), free(cs), free(cl), free(blocked_pair), free(blocked_space), free(blocked_conn), free(od), free(os_);
-    free(ol);
-    Py_DECREF(dgs);
-    Py_XDECREF(route);
+    walk_state_clear(&ws);
     Py_XDECREF(walked);
+    Py_XDECREF(rolled);
     Py_XDECREF(recs);
     Py_XDECREF(deferred);
-    Py_XDECREF(sexp_out);
-    Py_XDECREF(closed_out);
-    Py_XDECREF(empty);
-    Py_XDECREF(minus1);
-    Py_XDECREF(zero);
-    Py_XDECREF(s_key);
-    Py_XDECREF(s_dec);
-    Py_XDECREF(s_rsv);
-    Py_XDECREF(s_closed);
+    return ret;
+}
+
+/* form: 0 receive_routed, 1 receive_accept, 2 receive_routed_phase, 3 receive_accept_reply */
+static PyObject *receive_routed_impl(PyObject *args, int form)
+{
+    static const Py_ssize_t n_args[4] = {15, 18, 16, 24};
+    Routed r;
+    memset(&r, 0, sizeof r);
+    if (PyTuple_Size(args) != n_args[form]) {
+        PyErr_Format(PyExc_TypeError, "function takes exactly %zd arguments (%zd given)", n_args[form],
+                     PyTuple_Size(args));
+        return NULL;
+    }
+    if (!parse_slice(args, 0, 15, "OOIO!y#y#y#y#y#y#OOOy#i", &r.t, &r.mo, &r.cid_len, &PyList_Type, &r.dgs, &r.a_pair,
+                     &r.l_pair, &r.a_space, &r.l_space, &r.a_pslot, &r.l_pslot, &r.a_sexp, &r.l_sexp, &r.a_kslot,
+                     &r.l_kslot, &r.a_kexp, &r.l_kexp, &r.rec_type, &r.ptype, &r.epoch, &r.a_closed, &r.l_closed,
+                     &r.walk))
+        return NULL;
+    r.phased = form == 2, r.accept = form == 1 || form == 3, r.reply = form == 3;
+    if (r.phased && !parse_slice(args, 15, 16, "y#", &r.a_pnext, &r.l_pnext)) return NULL;
+    if (r.accept && !parse_slice(args, 15, 18, "y#y#I", &r.a_arow, &r.l_arow, &r.a_aslot, &r.l_aslot, &r.accept_flags))
+        return NULL;
+    if (r.reply && !parse_slice(args, 18, 24, "Oy#y#Ky#I", &r.rt, &r.a_addr, &r.l_addr, &r.a_rand, &r.l_rand,
+                                &r.token_ctr, &r.a_vers, &r.l_vers, &r.reply_flags))
+        return NULL;
+    PyObject *ret = NULL;
+    if (routed_prepare(&r) == 0 && routed_launch(&r) == 0) ret = routed_result(&r);
+    scratch_free_all(&r.sc);
+    Py_XDECREF(r.snap);
+    Py_XDECREF(r.route);
+    Py_XDECREF(r.acc);
+    Py_XDECREF(r.km);
+    Py_XDECREF(r.secrets);
+    Py_XDECREF(r.rbuf);
+    Py_XDECREF(r.rrec);
     return ret;
 }
 
@@ -3124,6 +2958,14 @@ PyMODINIT_FUNC PyInit__crypto(void)
         add_type(m, &Multi_spec, "MultiSession", &g_multi_type) < 0 ||
         add_type(m, &CidMap_spec, "CidMap", &g_cidmap_type) < 0)
         return NULL;
+    g_empty = PyBytes_FromStringAndSize("", 0);
+    g_minus1 = PyLong_FromLong(-1);
+    g_zero = PyLong_FromLong(0);
+    g_s_key = PyUnicode_FromString("key_unavailable");
+    g_s_dec = PyUnicode_FromString("payload_decrypt_error");
+    g_s_rsv = PyUnicode_FromString("reserved_bits");
+    g_s_closed = PyUnicode_FromString("connection_closed");
+    if (!g_empty || !g_minus1 || !g_zero || !g_s_key || !g_s_dec || !g_s_rsv || !g_s_closed) return NULL;
     PyModule_AddIntConstant(m, "DESC_SIZE", (long)sizeof(qpp_desc));
     PyModule_AddIntConstant(m, "RESULT_SIZE", (long)sizeof(qpp_result));
     PyModule_AddIntConstant(m, "KEY_MATERIAL_SIZE", (long)sizeof(qpp_key_material));

@@ -77,7 +77,7 @@ def test_golden_generator_restatement_matches_reference_rows():
 
 
 def test_receive_walk_c_decode_matches_reference_rows():
-    """decode_pn_signed of the binding's receive walks (_crypto_ext.c), which
+    """decode_pn_signed of the binding's receive walks (csrc/qpp_rxwalk.h), which
     always takes a 4-byte number the signed way and reports a negative result
     as -1, through its test hook."""
     from aioquic_amd import _crypto
