@@ -194,6 +194,33 @@ class PacketEngine:
                             int(token_ctr), np.asarray(versions, np.uint32).tobytes(), int(reply_flags), _ptr(reply),
                             _ptr(seal), _ptr(tag), _ptr(rec), PacketEngine._stream(stream))
 
+    @staticmethod
+    def route_token(offs, lens, n: int, inbuf, route, long_idx, n_long: int, walk, walk_n, acc_row, n_acc: int,
+                    tokdesc, tokrec, accept_flags: int = L.A_NEED_TOKEN, stream=None) -> None:
+        """qpp_route_token on device buffers, after route() and route_walk()
+        on the same stream: where the Retry token of every candidate's Initial
+        lies, as AEAD-only DESC records (`tokdesc`) for unprotect() of the
+        reply key table -- from `inbuf` into a token buffer of TOKEN_STRIDE
+        bytes per candidate -- and the tokens' preliminary TOKEN_REC records
+        (`tokrec`)."""
+        _crypto.route_token(_ptr(offs), _ptr(lens), int(n), _ptr(inbuf), _ptr(route), _ptr(long_idx), int(n_long),
+                            _ptr(walk), _ptr(walk_n), _ptr(acc_row), int(n_acc), int(accept_flags), _ptr(tokdesc),
+                            _ptr(tokrec), PacketEngine._stream(stream))
+
+    def route_accept_tokens(self, offs, lens, n: int, inbuf, route, long_idx, n_long: int, walk, walk_n, acc_row,
+                            acc_slot, n_acc: int, addr, tok, tokres, ini, desc, acc, tokrec,
+                            accept_flags: int = L.A_NEED_TOKEN, flags: int = 0, stream=None) -> None:
+        """qpp_route_accept_tokens on device buffers, after route_token() and
+        the unprotect() of its descriptors on the same stream: route_accept()
+        with the tokens' verdicts.  `addr` (20 bytes per candidate), `tok`
+        (the opened tokens) and `tokres` (their RESULT records) are read;
+        `tokrec` is read and rewritten with the final TOKEN_REC records.  A
+        candidate whose token fails is ACC_BAD_TOKEN: no keys, no descriptor."""
+        _crypto.route_accept_tokens(_ptr(offs), _ptr(lens), int(n), _ptr(inbuf), _ptr(route), _ptr(long_idx),
+                                    int(n_long), _ptr(walk), _ptr(walk_n), _ptr(acc_row), _ptr(acc_slot), int(n_acc),
+                                    int(accept_flags), int(flags), _ptr(addr), _ptr(tok), _ptr(tokres), _ptr(ini),
+                                    _ptr(desc), _ptr(acc), _ptr(tokrec), self._stream(stream))
+
     def route_walk_unprotect_host(self, cid_map, cid_len: int, offs, lens, data, long_idx, conn_slot,
                                   conn_expected, out_len: int, flags: int = 0):
         """Route, walk the long-header datagrams `long_idx` and unprotect a

@@ -36,6 +36,7 @@
  *                        flags, out_len) -> (out, desc, route, results)
  *   receive_routed(...)                             receive.receive_routed's C path
  *   route_reply(...), receive_accept_reply(...)     Retry / Version Negotiation replies built on the device
+ *   route_token(...), route_accept_tokens(...), receive_serve(...)   Retry tokens validated on the device
  *   route_accept(...), receive_accept(...)          unrouted Initials accepted on the device:
  *                                                   the device form, receive.accept_routed's C path
  *
@@ -1309,6 +1310,56 @@ static PyObject *py_route_reply_launches(PyObject *m, PyObject *unused)
     return PyLong_FromUnsignedLongLong(qpp_route_reply_launches());
 }
 
+/* route_token(off_ptr, len_ptr, n, in_ptr, route_ptr, long_ptr, n_long, walk_ptr, walk_n_ptr, row_ptr, n_acc,
+ *             accept_flags, tokdesc_ptr, tokrec_ptr, stream) */
+static PyObject *py_route_token(PyObject *m, PyObject *args)
+{
+    unsigned long long op, lp, ip, rp, xp, wp, wnp, arp, tdp, trp, sp;
+    unsigned int n, n_long, n_acc, accept_flags;
+    if (!PyArg_ParseTuple(args, "KKIKKKIKKKIIKKK", &op, &lp, &n, &ip, &rp, &xp, &n_long, &wp, &wnp, &arp, &n_acc,
+                          &accept_flags, &tdp, &trp, &sp))
+        return NULL;
+    int rc = qpp_route_token(as_ptr(op), as_ptr(lp), n, as_ptr(ip), as_ptr(rp), as_ptr(xp), n_long, as_ptr(wp),
+                             as_ptr(wnp), as_ptr(arp), n_acc, accept_flags, as_ptr(tdp), as_ptr(trp), as_ptr(sp));
+    if (rc == QPP_E_ARG) {
+        PyErr_SetString(PyExc_ValueError, "bad route_token arguments (a null buffer, or an unknown accept flag)");
+        return NULL;
+    }
+    if (check_rc(rc) < 0) return NULL;
+    Py_RETURN_NONE;
+}
+
+static PyObject *py_route_token_launches(PyObject *m, PyObject *unused)
+{
+    return PyLong_FromUnsignedLongLong(qpp_route_token_launches());
+}
+
+/* route_accept_tokens(the arguments of route_accept up to desc_flags, addr_ptr, tok_ptr, tokres_ptr, ini_ptr,
+ *                     desc_ptr, acc_ptr, tokrec_ptr, stream) */
+static PyObject *py_route_accept_tokens(PyObject *m, PyObject *args)
+{
+    unsigned long long op, lp, ip, rp, xp, wp, wnp, arp, asp, adp, tkp, trsp, inip, dp, accp, trp, sp;
+    unsigned int n, n_long, n_acc, accept_flags, flags;
+    if (!PyArg_ParseTuple(args, "KKIKKKIKKKKIIIKKKKKKKK", &op, &lp, &n, &ip, &rp, &xp, &n_long, &wp, &wnp, &arp, &asp,
+                          &n_acc, &accept_flags, &flags, &adp, &tkp, &trsp, &inip, &dp, &accp, &trp, &sp))
+        return NULL;
+    if (flags > 0xffff) {
+        PyErr_SetString(PyExc_ValueError, "descriptor flags are 16 bits");
+        return NULL;
+    }
+    int rc = qpp_route_accept_tokens(as_ptr(op), as_ptr(lp), n, as_ptr(ip), as_ptr(rp), as_ptr(xp), n_long,
+                                     as_ptr(wp), as_ptr(wnp), as_ptr(arp), as_ptr(asp), n_acc, accept_flags,
+                                     (uint16_t)flags, as_ptr(adp), as_ptr(tkp), as_ptr(trsp), as_ptr(inip), as_ptr(dp),
+                                     as_ptr(accp), as_ptr(trp), as_ptr(sp));
+    if (rc == QPP_E_ARG) {
+        PyErr_SetString(PyExc_ValueError,
+                        "bad route_accept_tokens arguments (a null buffer, or an unknown accept flag)");
+        return NULL;
+    }
+    if (check_rc(rc) < 0) return NULL;
+    Py_RETURN_NONE;
+}
+
 static int host_call(int enc, qpp_keytab *kt, const void *desc, uint32_t n, const void *in,
                      size_t in_len, void *out, size_t out_len, void *res)
 {
@@ -2350,6 +2401,14 @@ done:
  * 16; the fifth item holds the 256 bytes and the packed qpp_reply_rec of
  * every candidate (zeros when no reply flag is set).
  *
+ * receive_serve(the arguments of receive_accept_reply)
+ *     -> (route, None, None | (...), (accept records, key material, secrets), (reply buffer, reply records),
+ *         token records)
+ * receive_accept_reply for a server in Retry mode that also validates the
+ * tokens that come back (asyncio/server.py:112-120): the call is
+ * qpp_session_serve_unprotect, and the sixth item holds the packed
+ * qpp_token_rec of every candidate.
+ *
  * receive_routed_phase(the arguments of receive_routed, pair_next_u32)
  *     -> (route, None | (records, deferred, space_exp after, conn_closed after, pair_rolled_u8), None | (...))
  * receive_routed with the peers' key updates resolved on the device: the call
@@ -2372,7 +2431,7 @@ typedef struct {
     unsigned int cid_len;
     int walk;
     /* the forms' tails: which were given, and what they hold */
-    int phased, accept, reply;
+    int phased, accept, reply, serve;
     PyObject *rt;
     const char *a_pnext, *a_arow, *a_aslot, *a_addr, *a_rand, *a_vers;
     Py_ssize_t l_pnext, l_arow, l_aslot, l_addr, l_rand, l_vers;
@@ -2399,7 +2458,7 @@ typedef struct {
     qpp_walk_rec *wrec;
     uint32_t *wn;
     uint8_t *phase, *hout;
-    PyObject *route, *acc, *km, *secrets, *rbuf, *rrec;
+    PyObject *route, *acc, *km, *secrets, *rbuf, *rrec, *trec;
     Scratch sc;
 } Routed;
 
@@ -2528,6 +2587,11 @@ static int routed_launch(Routed *r)
         memset(PyBytes_AsString(r->rbuf), 0, (size_t)na * QPP_REPLY_STRIDE);
         memset(PyBytes_AsString(r->rrec), 0, (size_t)na * sizeof(qpp_reply_rec));
     }
+    if (r->serve) {
+        r->trec = PyBytes_FromStringAndSize(NULL, na * (Py_ssize_t)sizeof(qpp_token_rec));
+        if (!r->trec) return -1;
+        memset(PyBytes_AsString(r->trec), 0, (size_t)na * sizeof(qpp_token_rec));
+    }
     size_t total = 0;
     uint32_t nl = 0;
     for (Py_ssize_t i = 0; i < n; ++i) {
@@ -2572,7 +2636,19 @@ static int routed_launch(Routed *r)
     int rc;
     Py_BEGIN_ALLOW_THREADS  /* the snapshot holds every datagram */
     par_copy(cd, cs, cl, (size_t)n, total);
-    if (r->reply) {
+    if (r->serve) {
+        refused = "bad accept, reply or token arguments (those of receive_accept_reply, Retry mode not set in both "
+                  "flags, or no addresses); nothing was launched";
+        rc = qpp_session_serve_unprotect(
+            ss, r->kt, r->map, r->cid_len, offs, lens, (uint32_t)n, hin, total, r->lidx, nl, r->kslot, r->kexp,
+            (uint32_t)r->nc, 0, (const uint32_t *)r->a_arow, (const uint32_t *)r->a_aslot, (uint32_t)na,
+            r->accept_flags, r->reply_kt, r->l_addr ? (const uint8_t *)r->a_addr : NULL, (const uint8_t *)r->a_rand,
+            r->token_ctr, (const uint32_t *)r->a_vers, (uint32_t)(r->l_vers / 4), r->reply_flags, r->hout, total,
+            r->desc, rr, r->res, r->wrec, r->wn, (qpp_accept_rec *)PyBytes_AsString(r->acc),
+            (qpp_key_material *)PyBytes_AsString(r->km), (uint8_t *)PyBytes_AsString(r->secrets),
+            (uint8_t *)PyBytes_AsString(r->rbuf), (qpp_reply_rec *)PyBytes_AsString(r->rrec),
+            (qpp_token_rec *)PyBytes_AsString(r->trec));
+    } else if (r->reply) {
         refused = "bad accept or reply arguments (those of receive_accept, a reply table of fewer than 3 slots, an "
                   "address length that is neither 6 nor 18, not 1..16 versions, an unknown reply flag, or a token "
                   "counter that wraps); nothing was launched";
@@ -2660,7 +2736,9 @@ static PyObject *routed_result(Routed *r)
         }
         PyObject *found = r->accept ? PyTuple_Pack(3, r->acc, r->km, r->secrets) : NULL;
         PyObject *sent = r->reply && found ? PyTuple_Pack(2, r->rbuf, r->rrec) : NULL;
-        if (sent) ret = PyTuple_Pack(5, r->route, Py_None, longs ? longs : Py_None, found, sent);
+        if (sent && r->serve)
+            ret = PyTuple_Pack(6, r->route, Py_None, longs ? longs : Py_None, found, sent, r->trec);
+        else if (sent) ret = PyTuple_Pack(5, r->route, Py_None, longs ? longs : Py_None, found, sent);
         else if (found && !r->reply) ret = PyTuple_Pack(4, r->route, Py_None, longs ? longs : Py_None, found);
         else if (!r->accept) ret = PyTuple_Pack(3, r->route, Py_None, longs ? longs : Py_None);
         Py_XDECREF(sent);
@@ -2697,10 +2775,10 @@ done:
     return ret;
 }
 
-/* form: 0 receive_routed, 1 receive_accept, 2 receive_routed_phase, 3 receive_accept_reply */
+/* form: 0 receive_routed, 1 receive_accept, 2 receive_routed_phase, 3 receive_accept_reply, 4 receive_serve */
 static PyObject *receive_routed_impl(PyObject *args, int form)
 {
-    static const Py_ssize_t n_args[4] = {15, 18, 16, 24};
+    static const Py_ssize_t n_args[5] = {15, 18, 16, 24, 24};
     Routed r;
     memset(&r, 0, sizeof r);
     if (PyTuple_Size(args) != n_args[form]) {
@@ -2713,7 +2791,7 @@ static PyObject *receive_routed_impl(PyObject *args, int form)
                      &r.l_kslot, &r.a_kexp, &r.l_kexp, &r.rec_type, &r.ptype, &r.epoch, &r.a_closed, &r.l_closed,
                      &r.walk))
         return NULL;
-    r.phased = form == 2, r.accept = form == 1 || form == 3, r.reply = form == 3;
+    r.phased = form == 2, r.accept = form == 1 || form >= 3, r.reply = form >= 3, r.serve = form == 4;
     if (r.phased && !parse_slice(args, 15, 16, "y#", &r.a_pnext, &r.l_pnext)) return NULL;
     if (r.accept && !parse_slice(args, 15, 18, "y#y#I", &r.a_arow, &r.l_arow, &r.a_aslot, &r.l_aslot, &r.accept_flags))
         return NULL;
@@ -2730,6 +2808,7 @@ static PyObject *receive_routed_impl(PyObject *args, int form)
     Py_XDECREF(r.secrets);
     Py_XDECREF(r.rbuf);
     Py_XDECREF(r.rrec);
+    Py_XDECREF(r.trec);
     return ret;
 }
 
@@ -2737,6 +2816,7 @@ static PyObject *py_receive_routed(PyObject *m, PyObject *args) { return receive
 static PyObject *py_receive_accept(PyObject *m, PyObject *args) { return receive_routed_impl(args, 1); }
 static PyObject *py_receive_routed_phase(PyObject *m, PyObject *args) { return receive_routed_impl(args, 2); }
 static PyObject *py_receive_accept_reply(PyObject *m, PyObject *args) { return receive_routed_impl(args, 3); }
+static PyObject *py_receive_serve(PyObject *m, PyObject *args) { return receive_routed_impl(args, 4); }
 
 /* long_dcids(datagrams) -> None when no bytes object of the list starts with
  * a long header (first byte, bit 7), else the set of the destination CIDs of
@@ -2853,6 +2933,11 @@ static PyMethodDef module_methods[] = {
     {"route_accept_launches", py_route_accept_launches, METH_NOARGS, "qpp_route_accept_launches()"},
     {"route_reply", py_route_reply, METH_VARARGS, "qpp_route_reply on device buffers"},
     {"route_reply_launches", py_route_reply_launches, METH_NOARGS, "qpp_route_reply_launches()"},
+    {"route_token", py_route_token, METH_VARARGS, "qpp_route_token on device buffers"},
+    {"route_token_launches", py_route_token_launches, METH_NOARGS, "qpp_route_token_launches()"},
+    {"route_accept_tokens", py_route_accept_tokens, METH_VARARGS, "qpp_route_accept_tokens on device buffers"},
+    {"receive_serve", py_receive_serve, METH_VARARGS,
+     "receive_accept_reply that also validates the Retry tokens that come back on the device"},
     {"receive_accept_reply", py_receive_accept_reply, METH_VARARGS,
      "receive_accept that also builds the Retry / Version Negotiation replies on the device"},
     {"receive_accept", py_receive_accept, METH_VARARGS,

@@ -22,6 +22,7 @@ namespace qpp_ac {
 
 // QPP_ACC_*
 constexpr uint8_t kOk = 0, kRouted = 1, kNotInitial = 2, kVersion = 3, kSmall = 4, kCid = 5, kNoToken = 6;
+constexpr uint8_t kBadToken = 7;             // QPP_ACC_BAD_TOKEN: only from qpp_route_accept_tokens
 constexpr uint32_t kNeedToken = 1u;          // QPP_A_NEED_TOKEN
 constexpr uint32_t kMinDatagram = 1200;      // SMALLEST_MAX_DATAGRAM_SIZE (server.py:91)
 constexpr uint32_t kSlotNone = 0xffffffffu;  // QPP_SLOT_NONE
@@ -64,16 +65,14 @@ QPP_HD inline uint8_t decide(uint32_t route_conn, uint8_t route_cls, uint32_t wa
     return kOk;
 }
 
-// Candidate a of datagram i (at p, len bytes, d_off[i] = off): its qpp_initial
-// and qpp_accept_rec, always, and its descriptor when the return value says
+// Candidate a of datagram i (at p, len bytes, d_off[i] = off) whose verdict is
+// st: its qpp_initial and qpp_accept_rec, always, and its descriptor when st is
 // kOk (d is left alone otherwise).  A rejected candidate's qpp_initial names
 // no slot and no CID: derived, never installed.
-QPP_HD inline uint8_t accept_one(uint32_t i, uint32_t route_conn, uint8_t route_cls, uint32_t walk_n,
-                                 const qpp_wk::Rec &w0, uint64_t off, uint32_t len, const uint8_t *p,
-                                 uint32_t slot_client, uint32_t slot_server, uint32_t accept_flags,
-                                 uint16_t desc_flags, Initial &ini, Desc &d, Acc &acc)
+QPP_HD inline uint8_t accept_fill(uint8_t st, uint32_t i, const qpp_wk::Rec &w0, uint64_t off, const uint8_t *p,
+                                  uint32_t slot_client, uint32_t slot_server, uint16_t desc_flags, Initial &ini,
+                                  Desc &d, Acc &acc)
 {
-    const uint8_t st = decide(route_conn, route_cls, walk_n, w0, len, accept_flags);
     ini.slot_client = ini.slot_server = kSlotNone;
     ini.cid_len = ini.flags = ini.rsv[0] = ini.rsv[1] = 0;
     for (uint32_t k = 0; k < qpp_wk::kCidMax; ++k) ini.cid[k] = 0;
@@ -101,6 +100,16 @@ QPP_HD inline uint8_t accept_one(uint32_t i, uint32_t route_conn, uint8_t route_
     acc.desc = i;
     acc.version = v2 ? 1 : 0;
     return st;
+}
+
+// decide, then accept_fill with its verdict.
+QPP_HD inline uint8_t accept_one(uint32_t i, uint32_t route_conn, uint8_t route_cls, uint32_t walk_n,
+                                 const qpp_wk::Rec &w0, uint64_t off, uint32_t len, const uint8_t *p,
+                                 uint32_t slot_client, uint32_t slot_server, uint32_t accept_flags,
+                                 uint16_t desc_flags, Initial &ini, Desc &d, Acc &acc)
+{
+    const uint8_t st = decide(route_conn, route_cls, walk_n, w0, len, accept_flags);
+    return accept_fill(st, i, w0, off, p, slot_client, slot_server, desc_flags, ini, d, acc);
 }
 
 }  // namespace qpp_ac

@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include <new>
+#include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -23,6 +24,7 @@
 #include "qpp_accept.h"
 #include "qpp_reply.h"
 #include "qpp_route.h"
+#include "qpp_token.h"
 #include "qpp_walk.h"
 
 using qpp_rt::Bucket;
@@ -54,6 +56,15 @@ static_assert(sizeof(qpp_reply_rec) == sizeof(qpp_rp::Rec) && QPP_REPLY_STRIDE =
               QPP_RP_OK == qpp_rp::kStOk && QPP_RP_BOUNDS == qpp_rp::kBounds && QPP_RP_ADDR == qpp_rp::kAddr &&
               QPP_F_NO_HP == qpp_rp::kNoHp && QPP_TAG_LEN == qpp_rp::kTagLen,
               "reply records");
+static_assert(sizeof(qpp_token_rec) == sizeof(qpp_tk::Rec) && sizeof(qpp_token_rec) == 48 &&
+              offsetof(qpp_token_rec, odcid) == 4 && offsetof(qpp_token_rec, rscid) == 24 &&
+              QPP_TOKEN_STRIDE == qpp_tk::kStride && QPP_TOKEN_MIN == qpp_tk::kTokenMin &&
+              QPP_TOKEN_MAX == qpp_tk::kTokenMax && QPP_TK_OK == qpp_tk::kOk && QPP_TK_NONE == qpp_tk::kNone &&
+              QPP_TK_LENGTH == qpp_tk::kLength && QPP_TK_BOUNDS == qpp_tk::kBounds && QPP_TK_AUTH == qpp_tk::kAuth &&
+              QPP_TK_FORM == qpp_tk::kForm && QPP_TK_ADDR == qpp_tk::kAddr &&
+              QPP_ACC_BAD_TOKEN == qpp_ac::kBadToken && QPP_ACC_BAD_TOKEN == QPP_ACC_NO_TOKEN + 1 &&
+              QPP_S_OK == qpp_tk::kResOk && QPP_TOKEN_MAX <= QPP_TOKEN_STRIDE && sizeof(qpp_result) == 16,
+              "token records");
 
 struct qpp_cidmap {
     HostMap host;
@@ -238,59 +249,110 @@ __global__ __launch_bounds__(kRouteWG) void k_walk(uint32_t cid_len, const uint6
     walk_n[r] = found;
 }
 
-// One lane per candidate (k_accept): the decision of
-// qpp_accept.h over the lane's own walk and route records, then its
-// qpp_initial, its accept record and, when accepted, its datagram's
-// descriptor.  No LDS, no atomics: lane a writes ini[a], acc[a] and desc[i] of
-// its own datagram i, and the rows are distinct.
-__global__ __launch_bounds__(kRouteWG) void k_accept(const uint64_t *off, const uint32_t *len, uint32_t n,
-                                                     const uint8_t *in, const qpp_route_rec *route,
-                                                     const uint32_t *long_idx, uint32_t n_long,
-                                                     const qpp_walk_rec *walk, const uint32_t *walk_n,
-                                                     const uint32_t *acc_row, const uint32_t *acc_slot,
-                                                     uint32_t n_acc, uint32_t accept_flags, uint32_t desc_flags,
-                                                     qpp_initial *ini, qpp_desc *desc, qpp_accept_rec *acc)
-{
-    const uint32_t a = blockIdx.x * kRouteWG + threadIdx.x;
-    if (a >= n_acc) return;
-    const uint32_t r = acc_row[a];
-    const uint32_t i = r < n_long ? long_idx[r] : n;
-    // a row or an index outside the batch (not the caller's contract): no
-    // record, so "not an Initial", and nothing of the batch is read
-    uint32_t conn = QPP_CONN_NONE, found = 0, l = 0;
-    uint8_t cls = QPP_R_LONG;
-    uint64_t o = 0;
+// A candidate's datagram and the records the walk and the route left of it:
+// what k_accept, k_token and k_reply start from.  A row or an index outside
+// the batch (not the caller's contract) has no record, so it is "not an
+// Initial", and nothing of the batch is read.
+struct Cand {
+    uint32_t i, conn, found, l;
+    uint8_t cls;
+    uint64_t o;
     qpp_wk::Rec w0;
-    w0.off = w0.len = w0.version = w0.desc = 0;
-    w0.pn_off = w0.token_len = 0;
-    w0.type = w0.status = w0.dcid_len = w0.scid_len = 0;
-    if (i < n) {
-        const qpp_route_rec rr = route[i];
-        conn = rr.conn;
-        cls = rr.cls;
-        found = walk_n[r];
-        o = off[i];
-        l = len[i];
-        if (found) {
+};
+
+__device__ inline Cand candidate(uint32_t a, const uint64_t *off, const uint32_t *len, uint32_t n,
+                                 const qpp_route_rec *route, const uint32_t *long_idx, uint32_t n_long,
+                                 const qpp_walk_rec *walk, const uint32_t *walk_n, const uint32_t *acc_row)
+{
+    Cand c;
+    const uint32_t r = acc_row[a];
+    c.i = r < n_long ? long_idx[r] : n;
+    c.conn = QPP_CONN_NONE, c.found = 0, c.l = 0;
+    c.cls = QPP_R_LONG;
+    c.o = 0;
+    c.w0.off = c.w0.len = c.w0.version = c.w0.desc = 0;
+    c.w0.pn_off = c.w0.token_len = 0;
+    c.w0.type = c.w0.status = c.w0.dcid_len = c.w0.scid_len = 0;
+    if (c.i < n) {
+        const qpp_route_rec rr = route[c.i];
+        c.conn = rr.conn;
+        c.cls = rr.cls;
+        c.found = walk_n[r];
+        c.o = off[c.i];
+        c.l = len[c.i];
+        if (c.found) {
             const qpp_walk_rec q = walk[(size_t)r * QPP_WALK_MAX];
-            w0.off = q.off;
-            w0.len = q.len;
-            w0.version = q.version;
-            w0.desc = q.desc;
-            w0.pn_off = q.pn_off;
-            w0.token_len = q.token_len;
-            w0.type = q.type;
-            w0.status = q.status;
-            w0.dcid_len = q.dcid_len;
-            w0.scid_len = q.scid_len;
+            c.w0.off = q.off;
+            c.w0.len = q.len;
+            c.w0.version = q.version;
+            c.w0.desc = q.desc;
+            c.w0.pn_off = q.pn_off;
+            c.w0.token_len = q.token_len;
+            c.w0.type = q.type;
+            c.w0.status = q.status;
+            c.w0.dcid_len = q.dcid_len;
+            c.w0.scid_len = q.scid_len;
         }
+    }
+    return c;
+}
+
+__device__ inline void store_desc(qpp_desc *dst, const qpp_ac::Desc &rd)
+{
+    qpp_desc d;
+    d.in_off = rd.in_off;
+    d.out_off = rd.out_off;
+    d.len = rd.len;
+    d.hdr_len = rd.hdr_len;
+    d.flags = rd.flags;
+    d.pn = rd.pn;
+    d.slot = rd.slot;
+    d.rsv = rd.rsv;
+    *dst = d;
+}
+
+// What a lane of the accepting kernels does (k_accept): the
+// decision of qpp_accept.h over the lane's own walk and route records, then
+// its qpp_initial, its accept record and, when accepted, its datagram's
+// descriptor.  TOKENS (k_accept_tokens): between the decision and the records,
+// the verdict of qpp_token.h on the token k_token located and the launch after
+// it opened; a candidate that fails it is QPP_ACC_BAD_TOKEN and is written as
+// any other rejection is.  No LDS, no atomics: lane a writes ini[a], acc[a],
+// tokrec[a] and desc[i] of its own datagram i, and the rows are distinct.
+template <bool TOKENS>
+__device__ __forceinline__ void accept_lane(uint32_t a, const uint64_t *off, const uint32_t *len, uint32_t n,
+                                            const uint8_t *in, const qpp_route_rec *route, const uint32_t *long_idx,
+                                            uint32_t n_long, const qpp_walk_rec *walk, const uint32_t *walk_n,
+                                            const uint32_t *acc_row, const uint32_t *acc_slot, uint32_t accept_flags,
+                                            uint32_t desc_flags, const uint8_t *addr, const uint8_t *tok,
+                                            const qpp_result *tokres, qpp_initial *ini, qpp_desc *desc,
+                                            qpp_accept_rec *acc, qpp_token_rec *tokrec)
+{
+    const Cand c = candidate(a, off, len, n, route, long_idx, n_long, walk, walk_n, acc_row);
+    uint8_t st = qpp_ac::decide(c.conn, c.cls, c.found, c.w0, c.l, accept_flags);
+    if (TOKENS) {
+        // the preliminary status is k_token's; a candidate that reaches the
+        // token test without one (kNone) was not examined and is not accepted
+        qpp_tk::Rec tr;
+        const bool tested = st == QPP_ACC_OK && (accept_flags & QPP_A_NEED_TOKEN);
+        const uint8_t pre = tested ? tokrec[a].status : (uint8_t)QPP_TK_NONE;
+        const uint8_t v = qpp_tk::check(pre, tested ? tokres[a].status : (uint16_t)QPP_S_OK, c.w0.token_len,
+                                        tok + (size_t)a * QPP_TOKEN_STRIDE, addr + (size_t)a * QPP_RP_ADDR_STRIDE, tr);
+        if (tested && v != QPP_TK_OK) st = QPP_ACC_BAD_TOKEN;
+        qpp_token_rec qt;
+        qt.status = tr.status;
+        qt.odcid_len = tr.odcid_len;
+        qt.rscid_len = tr.rscid_len;
+        qt.rsv = 0;
+        for (uint32_t k = 0; k < QPP_CID_MAX; ++k) qt.odcid[k] = tr.odcid[k], qt.rscid[k] = tr.rscid[k];
+        for (uint32_t k = 0; k < 4; ++k) qt.rsv2[k] = 0;
+        tokrec[a] = qt;
     }
     qpp_ac::Initial ri;
     qpp_ac::Desc rd;
     qpp_ac::Acc ra;
-    const uint8_t st = qpp_ac::accept_one(i, conn, cls, found, w0, o, l, in + o, acc_slot[2 * (size_t)a],
-                                          acc_slot[2 * (size_t)a + 1], accept_flags, (uint16_t)desc_flags, ri, rd,
-                                          ra);
+    qpp_ac::accept_fill(st, c.i, c.w0, c.o, in + c.o, acc_slot[2 * (size_t)a], acc_slot[2 * (size_t)a + 1],
+                        (uint16_t)desc_flags, ri, rd, ra);
     qpp_initial qi;
     qi.slot_client = ri.slot_client;
     qi.slot_server = ri.slot_server;
@@ -305,18 +367,63 @@ __global__ __launch_bounds__(kRouteWG) void k_accept(const uint64_t *off, const 
     qa.version = ra.version;
     qa.rsv[0] = qa.rsv[1] = 0;
     acc[a] = qa;
-    if (st == QPP_ACC_OK) {  // i < n: an accepted candidate has a route record
-        qpp_desc d;
-        d.in_off = rd.in_off;
-        d.out_off = rd.out_off;
-        d.len = rd.len;
-        d.hdr_len = rd.hdr_len;
-        d.flags = rd.flags;
-        d.pn = rd.pn;
-        d.slot = rd.slot;
-        d.rsv = rd.rsv;
-        desc[i] = d;
-    }
+    if (st == QPP_ACC_OK) store_desc(&desc[c.i], rd);  // i < n: an accepted candidate has a route record
+}
+
+__global__ __launch_bounds__(kRouteWG) void k_accept(const uint64_t *off, const uint32_t *len, uint32_t n,
+                                                     const uint8_t *in, const qpp_route_rec *route,
+                                                     const uint32_t *long_idx, uint32_t n_long,
+                                                     const qpp_walk_rec *walk, const uint32_t *walk_n,
+                                                     const uint32_t *acc_row, const uint32_t *acc_slot,
+                                                     uint32_t n_acc, uint32_t accept_flags, uint32_t desc_flags,
+                                                     qpp_initial *ini, qpp_desc *desc, qpp_accept_rec *acc)
+{
+    const uint32_t a = blockIdx.x * kRouteWG + threadIdx.x;
+    if (a >= n_acc) return;
+    accept_lane<false>(a, off, len, n, in, route, long_idx, n_long, walk, walk_n, acc_row, acc_slot, accept_flags,
+                       desc_flags, NULL, NULL, NULL, ini, desc, acc, NULL);
+}
+
+__global__ __launch_bounds__(kRouteWG) void k_accept_tokens(
+    const uint64_t *off, const uint32_t *len, uint32_t n, const uint8_t *in, const qpp_route_rec *route,
+    const uint32_t *long_idx, uint32_t n_long, const qpp_walk_rec *walk, const uint32_t *walk_n,
+    const uint32_t *acc_row, const uint32_t *acc_slot, uint32_t n_acc, uint32_t accept_flags, uint32_t desc_flags,
+    const uint8_t *addr, const uint8_t *tok, const qpp_result *tokres, qpp_initial *ini, qpp_desc *desc,
+    qpp_accept_rec *acc, qpp_token_rec *tokrec)
+{
+    const uint32_t a = blockIdx.x * kRouteWG + threadIdx.x;
+    if (a >= n_acc) return;
+    accept_lane<true>(a, off, len, n, in, route, long_idx, n_long, walk, walk_n, acc_row, acc_slot, accept_flags,
+                      desc_flags, addr, tok, tokres, ini, desc, acc, tokrec);
+}
+
+// One lane per candidate (k_token): where the token of the
+// lane's own Initial lies (qpp_token.h), as the AEAD-only descriptor that
+// opens it from the datagram buffer into the lane's own 128 bytes of the token
+// buffer, and the token's preliminary status.  Byte loads of the lane's own
+// header only, each behind a check against the datagram's length; the datagram
+// buffer is not written.  No LDS, no atomics: lane a writes tokdesc[a] and
+// tokrec[a].
+__global__ __launch_bounds__(kRouteWG) void k_token(const uint64_t *off, const uint32_t *len, uint32_t n,
+                                                    const uint8_t *in, const qpp_route_rec *route,
+                                                    const uint32_t *long_idx, uint32_t n_long,
+                                                    const qpp_walk_rec *walk, const uint32_t *walk_n,
+                                                    const uint32_t *acc_row, uint32_t n_acc, uint32_t accept_flags,
+                                                    qpp_desc *tokdesc, qpp_token_rec *tokrec)
+{
+    const uint32_t a = blockIdx.x * kRouteWG + threadIdx.x;
+    if (a >= n_acc) return;
+    const Cand c = candidate(a, off, len, n, route, long_idx, n_long, walk, walk_n, acc_row);
+    const uint8_t st = qpp_ac::decide(c.conn, c.cls, c.found, c.w0, c.l, accept_flags);
+    qpp_ac::Desc rd;
+    const uint8_t pre = qpp_tk::token_desc(a, st, accept_flags, c.w0, c.o, c.l, in + c.o, rd);
+    store_desc(&tokdesc[a], rd);
+    qpp_token_rec qt;
+    qt.status = pre;
+    qt.odcid_len = qt.rscid_len = qt.rsv = 0;
+    for (uint32_t k = 0; k < QPP_CID_MAX; ++k) qt.odcid[k] = qt.rscid[k] = 0;
+    for (uint32_t k = 0; k < 4; ++k) qt.rsv2[k] = 0;
+    tokrec[a] = qt;
 }
 
 // The supported versions of a Version Negotiation reply, by value among the
@@ -394,6 +501,7 @@ __global__ __launch_bounds__(kRouteWG) void k_reply(const uint64_t *off, const u
 std::atomic<uint64_t> g_walk_launches{0};
 std::atomic<uint64_t> g_accept_launches{0};
 std::atomic<uint64_t> g_reply_launches{0};
+std::atomic<uint64_t> g_token_launches{0};
 
 void map_entries(const qpp_cid_entry *e, uint32_t n, std::vector<HostMap::Entry> &v)
 {
@@ -583,6 +691,49 @@ int qpp_route_accept(const uint64_t *d_off, const uint32_t *d_len, uint32_t n, c
 
 uint64_t qpp_route_accept_launches(void) { return g_accept_launches.load(std::memory_order_relaxed); }
 
+int qpp_route_token(const uint64_t *d_off, const uint32_t *d_len, uint32_t n, const uint8_t *d_in,
+                    const qpp_route_rec *d_route, const uint32_t *d_long_idx, uint32_t n_long,
+                    const qpp_walk_rec *d_walk, const uint32_t *d_walk_n, const uint32_t *d_acc_row, uint32_t n_acc,
+                    uint32_t accept_flags, qpp_desc *d_tokdesc, qpp_token_rec *d_tokrec, void *stream)
+{
+    if (accept_flags & ~QPP_A_NEED_TOKEN) return QPP_E_ARG;
+    if (n_acc == 0) return QPP_OK;
+    if (n_acc > (1u << 24)) return QPP_E_ARG;
+    if (!d_off || !d_len || !d_in || !d_route || !d_long_idx || !d_walk || !d_walk_n || !d_acc_row || !d_tokdesc ||
+        !d_tokrec)
+        return QPP_E_ARG;
+    hipLaunchKernelGGL(k_token, dim3((n_acc + kRouteWG - 1) / kRouteWG), dim3(kRouteWG), 0, (hipStream_t)stream,
+                       d_off, d_len, n, d_in, d_route, d_long_idx, n_long, d_walk, d_walk_n, d_acc_row, n_acc,
+                       accept_flags, d_tokdesc, d_tokrec);
+    HIPCHK(hipGetLastError());
+    g_token_launches.fetch_add(1, std::memory_order_relaxed);
+    return QPP_OK;
+}
+
+uint64_t qpp_route_token_launches(void) { return g_token_launches.load(std::memory_order_relaxed); }
+
+int qpp_route_accept_tokens(const uint64_t *d_off, const uint32_t *d_len, uint32_t n, const uint8_t *d_in,
+                            const qpp_route_rec *d_route, const uint32_t *d_long_idx, uint32_t n_long,
+                            const qpp_walk_rec *d_walk, const uint32_t *d_walk_n, const uint32_t *d_acc_row,
+                            const uint32_t *d_acc_slot, uint32_t n_acc, uint32_t accept_flags, uint16_t desc_flags,
+                            const uint8_t *d_addr, const uint8_t *d_tok, const qpp_result *d_tokres,
+                            qpp_initial *d_ini, qpp_desc *d_desc, qpp_accept_rec *d_acc, qpp_token_rec *d_tokrec,
+                            void *stream)
+{
+    if (accept_flags & ~QPP_A_NEED_TOKEN) return QPP_E_ARG;
+    if (n_acc == 0) return QPP_OK;
+    if (!d_off || !d_len || !d_in || !d_route || !d_long_idx || !d_walk || !d_walk_n || !d_acc_row || !d_acc_slot ||
+        !d_addr || !d_tok || !d_tokres || !d_ini || !d_desc || !d_acc || !d_tokrec)
+        return QPP_E_ARG;
+    hipLaunchKernelGGL(k_accept_tokens, dim3((n_acc + kRouteWG - 1) / kRouteWG), dim3(kRouteWG), 0,
+                       (hipStream_t)stream, d_off, d_len, n, d_in, d_route, d_long_idx, n_long, d_walk, d_walk_n,
+                       d_acc_row, d_acc_slot, n_acc, accept_flags, (uint32_t)desc_flags, d_addr, d_tok, d_tokres,
+                       d_ini, d_desc, d_acc, d_tokrec);
+    HIPCHK(hipGetLastError());
+    g_accept_launches.fetch_add(1, std::memory_order_relaxed);
+    return QPP_OK;
+}
+
 int qpp_route_reply(const uint64_t *d_off, const uint32_t *d_len, uint32_t n, const uint8_t *d_in,
                     const uint32_t *d_long_idx, uint32_t n_long, const qpp_walk_rec *d_walk,
                     const uint32_t *d_acc_row, const qpp_accept_rec *d_acc, uint32_t n_acc, const uint8_t *d_addr,
@@ -629,6 +780,11 @@ struct ReplyArgs {
     qpp_reply_rec *reply_rec_out;
 };
 
+// The token step of qpp_session_serve_unprotect, beside AcceptArgs and ReplyArgs.
+struct TokenArgs {
+    qpp_token_rec *tokrec_out;
+};
+
 // The session forms.  walk_form: conn_slot / conn_expected are the walk's
 // per-key-set and per-space arrays, and the routing kernel's per-connection
 // ones (the 1-RTT slot, the application space's number) are taken from them.
@@ -637,17 +793,24 @@ struct ReplyArgs {
 // rp (with ac's candidates only; NULL or no flag: nothing of it happens): the
 // assembling kernel after the accepting one, the two reply protects after the
 // batch's unprotect.
+// tk (with ac and rp, Retry mode only): the locating kernel and the tokens'
+// unprotect ahead of the accepting kernel, which then runs with their verdicts.
 static int route_unprotect(qpp_session *s, const qpp_keytab *kt, const qpp_cidmap *m, uint32_t cid_len,
                            const uint64_t *off, const uint32_t *len, uint32_t n, const uint8_t *in, size_t in_len,
                            bool walk_form, const uint32_t *long_idx, uint32_t n_long, const uint32_t *conn_slot,
                            const uint64_t *conn_expected, uint32_t n_conn, uint16_t desc_flags, uint8_t *out,
                            size_t out_len, qpp_desc *desc_out, qpp_route_rec *route_out, qpp_result *res,
                            qpp_walk_rec *walk_out, uint32_t *walk_n_out, const AcceptArgs *ac = NULL,
-                           const uint32_t *conn_next = NULL, uint8_t *phase_out = NULL, const ReplyArgs *rp = NULL)
+                           const uint32_t *conn_next = NULL, uint8_t *phase_out = NULL, const ReplyArgs *rp = NULL,
+                           const TokenArgs *tk = NULL)
 {
     if (!s || !kt || !m || cid_len < 1 || cid_len > QPP_CID_MAX) return QPP_E_ARG;
     const uint32_t n_acc = ac ? ac->n : 0;
     if (ac && (ac->flags & ~QPP_A_NEED_TOKEN)) return QPP_E_ARG;
+    // the tokens are a Retry-mode server's: both flags, the table with the token key, the addresses
+    if (tk && (!ac || !rp || !(ac->flags & QPP_A_NEED_TOKEN) || !(rp->reply_flags & QPP_RP_RETRY) || !rp->reply_kt ||
+               qpp_keytab_capacity(rp->reply_kt) < 3 || (n_acc && (!rp->addr || !tk->tokrec_out))))
+        return QPP_E_ARG;
     if (n == 0) return n_long || n_acc ? QPP_E_ARG : QPP_OK;
     if (!off || !len || !route_out || !res || (in_len && !in) || (out_len && !out) ||
         (n_conn && (!conn_slot || !conn_expected)))
@@ -692,6 +855,7 @@ static int route_unprotect(qpp_session *s, const qpp_keytab *kt, const qpp_cidma
         }
     }
     const bool replies = rp && n_acc && rp->reply_flags;
+    const bool tokens = tk && n_acc;  // then replies too: QPP_RP_RETRY is set
     if (replies) {
         const bool retry = rp->reply_flags & QPP_RP_RETRY;
         if ((rp->reply_flags & ~(QPP_RP_VN | QPP_RP_RETRY)) || !rp->reply_kt || !rp->rnd || !rp->reply_out ||
@@ -730,14 +894,20 @@ static int route_unprotect(qpp_session *s, const qpp_keytab *kt, const qpp_cidma
                  o_reply = o_phase + (any_next ? al256((size_t)n) : 0),
                  o_rrec = o_reply + (replies ? (size_t)n_acc * QPP_REPLY_STRIDE : 0),
                  o_rres = o_rrec + (replies ? al256((size_t)n_acc * sizeof(qpp_reply_rec)) : 0),
-                 down = o_rres + (replies ? al256((size_t)n_acc * 2 * sizeof(qpp_result)) : 0);
+                 o_trec = o_rres + (replies ? al256((size_t)n_acc * 2 * sizeof(qpp_result)) : 0),
+                 down = o_trec + (tokens ? al256((size_t)n_acc * sizeof(qpp_token_rec)) : 0);
     // the candidates' qpp_initial records and the reply descriptors (the seals,
     // then the tags) never leave the device: scratch past both copies
     const size_t ini_bytes = n_acc ? al256((size_t)n_acc * sizeof(qpp_initial)) : 0;
     const size_t rdesc_bytes = replies ? al256((size_t)n_acc * 2 * sizeof(qpp_desc)) : 0;
+    // nor do the tokens' descriptors, their opened bytes and the results of the launch that opens them
+    const size_t tdesc_bytes = tokens ? al256((size_t)n_acc * sizeof(qpp_desc)) : 0;
+    const size_t tok_bytes = tokens ? al256((size_t)n_acc * QPP_TOKEN_STRIDE) : 0;
+    const size_t tres_bytes = tokens ? al256((size_t)n_acc * sizeof(qpp_result)) : 0;
     qpp_session_bufs b;
     const size_t need = in_len > out_len ? in_len : out_len;
-    int rc = qpp_internal_session_bufs(s, need, nd, up + down + ini_bytes + rdesc_bytes, &b);
+    const size_t device_only = ini_bytes + rdesc_bytes + tdesc_bytes + tok_bytes + tres_bytes;
+    int rc = qpp_internal_session_bufs(s, need, nd, up + down + device_only, &b);
     if (rc != QPP_OK) return rc;
     uint8_t *hu = b.h_scratch, *du = b.d_scratch, *hd = b.h_scratch + up, *dd = b.d_scratch + up;
     memcpy(hu, off, (size_t)n * 8);
@@ -791,11 +961,33 @@ static int route_unprotect(qpp_session *s, const qpp_keytab *kt, const qpp_cidma
     }
     if (n_acc) {
         qpp_initial *d_ini = (qpp_initial *)(dd + down);
-        rc = qpp_route_accept((const uint64_t *)du, (const uint32_t *)(du + o_len), n, b.d_in, d_route,
-                              (const uint32_t *)(du + o_long), n_long, (const qpp_walk_rec *)(dd + o_walk),
-                              (const uint32_t *)(dd + o_walkn), (const uint32_t *)(du + o_arow),
-                              (const uint32_t *)(du + o_aslot), n_acc, ac->flags, desc_flags, d_ini, d_desc,
-                              (qpp_accept_rec *)(dd + o_acc), b.stream);
+        if (tokens) {
+            // the datagram buffer is only read: a token is part of its Initial's AAD
+            qpp_desc *d_tdesc = (qpp_desc *)(dd + down + ini_bytes + rdesc_bytes);
+            uint8_t *d_tok = dd + down + ini_bytes + rdesc_bytes + tdesc_bytes;
+            qpp_result *d_tres = (qpp_result *)(d_tok + tok_bytes);
+            qpp_token_rec *d_trec = (qpp_token_rec *)(dd + o_trec);
+            HIPCHK(hipMemsetAsync(d_tok, 0, tok_bytes + tres_bytes, b.stream));
+            rc = qpp_route_token((const uint64_t *)du, (const uint32_t *)(du + o_len), n, b.d_in, d_route,
+                                 (const uint32_t *)(du + o_long), n_long, (const qpp_walk_rec *)(dd + o_walk),
+                                 (const uint32_t *)(dd + o_walkn), (const uint32_t *)(du + o_arow), n_acc, ac->flags,
+                                 d_tdesc, d_trec, b.stream);
+            if (rc != QPP_OK) return rc;
+            rc = qpp_unprotect(rp->reply_kt, d_tdesc, n_acc, b.d_in, d_tok, d_tres, b.stream);
+            if (rc != QPP_OK) return rc;
+            rc = qpp_route_accept_tokens((const uint64_t *)du, (const uint32_t *)(du + o_len), n, b.d_in, d_route,
+                                         (const uint32_t *)(du + o_long), n_long, (const qpp_walk_rec *)(dd + o_walk),
+                                         (const uint32_t *)(dd + o_walkn), (const uint32_t *)(du + o_arow),
+                                         (const uint32_t *)(du + o_aslot), n_acc, ac->flags, desc_flags, du + o_addr,
+                                         d_tok, d_tres, d_ini, d_desc, (qpp_accept_rec *)(dd + o_acc), d_trec,
+                                         b.stream);
+        } else {
+            rc = qpp_route_accept((const uint64_t *)du, (const uint32_t *)(du + o_len), n, b.d_in, d_route,
+                                  (const uint32_t *)(du + o_long), n_long, (const qpp_walk_rec *)(dd + o_walk),
+                                  (const uint32_t *)(dd + o_walkn), (const uint32_t *)(du + o_arow),
+                                  (const uint32_t *)(du + o_aslot), n_acc, ac->flags, desc_flags, d_ini, d_desc,
+                                  (qpp_accept_rec *)(dd + o_acc), b.stream);
+        }
         if (rc != QPP_OK) return rc;
         if (replies) {
             qpp_desc *d_seal = (qpp_desc *)(dd + down + ini_bytes);
@@ -851,6 +1043,7 @@ static int route_unprotect(qpp_session *s, const qpp_keytab *kt, const qpp_cidma
     if (replies) {
         memcpy(rp->reply_out, hd + o_reply, (size_t)n_acc * QPP_REPLY_STRIDE);
         memcpy(rp->reply_rec_out, hd + o_rrec, (size_t)n_acc * sizeof(qpp_reply_rec));
+        if (tokens) memcpy(tk->tokrec_out, hd + o_trec, (size_t)n_acc * sizeof(qpp_token_rec));
         // a Retry is whole or it is not sent
         const qpp_result *rres = (const qpp_result *)(hd + o_rres);
         for (uint32_t a = 0; a < n_acc; ++a) {
@@ -947,6 +1140,27 @@ int qpp_session_accept_reply_unprotect(qpp_session *s, qpp_keytab *kt, const qpp
     return settle(s, route_unprotect(s, kt, m, cid_len, off, len, n, in, in_len, true, long_idx, n_long, conn_slot,
                                      conn_expected, n_conn, desc_flags, out, out_len, desc_out, route_out, res,
                                      walk_out, walk_n_out, &ac, NULL, NULL, &rp));
+}
+
+int qpp_session_serve_unprotect(qpp_session *s, qpp_keytab *kt, const qpp_cidmap *m, uint32_t cid_len,
+                                const uint64_t *off, const uint32_t *len, uint32_t n, const uint8_t *in,
+                                size_t in_len, const uint32_t *long_idx, uint32_t n_long,
+                                const uint32_t *conn_slot, const uint64_t *conn_expected, uint32_t n_conn,
+                                uint16_t desc_flags, const uint32_t *acc_row, const uint32_t *acc_slot,
+                                uint32_t n_acc, uint32_t accept_flags, const qpp_keytab *reply_kt,
+                                const uint8_t *addr, const uint8_t *rnd, uint64_t token_ctr,
+                                const uint32_t *versions, uint32_t n_versions, uint32_t reply_flags, uint8_t *out,
+                                size_t out_len, qpp_desc *desc_out, qpp_route_rec *route_out, qpp_result *res,
+                                qpp_walk_rec *walk_out, uint32_t *walk_n_out, qpp_accept_rec *acc_out,
+                                qpp_key_material *km_out, uint8_t *secrets_out, uint8_t *reply_out,
+                                qpp_reply_rec *reply_rec_out, qpp_token_rec *tokrec_out)
+{
+    const AcceptArgs ac = {kt, acc_row, acc_slot, n_acc, accept_flags, acc_out, km_out, secrets_out};
+    const ReplyArgs rp = {reply_kt, addr, rnd, token_ctr, versions, n_versions, reply_flags, reply_out, reply_rec_out};
+    const TokenArgs tk = {tokrec_out};
+    return settle(s, route_unprotect(s, kt, m, cid_len, off, len, n, in, in_len, true, long_idx, n_long, conn_slot,
+                                     conn_expected, n_conn, desc_flags, out, out_len, desc_out, route_out, res,
+                                     walk_out, walk_n_out, &ac, NULL, NULL, &rp, &tk));
 }
 
 }  // extern "C"

@@ -116,7 +116,16 @@ RP_KIND_NONE, RP_KIND_VN, RP_KIND_RETRY = 0, 1, 2
 RP_OK, RP_BOUNDS, RP_ADDR = 0, 0x40, 0x41
 # the reply key table's slots: the Retry keys of versions 1 and 2, the server's token key
 RP_SLOT_V1, RP_SLOT_V2, RP_SLOT_TOKEN = 0, 1, 2
-assert REPLY.itemsize == 8
+# qpp_token_rec: the device's verdict on the Retry token of one candidate
+# (qpp_route_token, qpp_route_accept_tokens): a TK_* status and, with TK_OK,
+# the two CIDs the token was sealed around; a candidate a token fails is
+# ACC_BAD_TOKEN.  TOKEN_STRIDE bytes of the token buffer per candidate
+TOKEN_REC = np.dtype([("status", "u1"), ("odcid_len", "u1"), ("rscid_len", "u1"), ("rsv", "u1"),
+                      ("odcid", "u1", (20,)), ("rscid", "u1", (20,)), ("rsv2", "u1", (4,))])
+TOKEN_STRIDE, TOKEN_MIN, TOKEN_MAX = 128, 27, 128
+ACC_BAD_TOKEN = 7
+TK_OK, TK_NONE, TK_LENGTH, TK_BOUNDS, TK_AUTH, TK_FORM, TK_ADDR = 0, 1, 2, 3, 4, 5, 6
+assert REPLY.itemsize == 8 and TOKEN_REC.itemsize == 48
 assert DESC.itemsize == 40 and RESULT.itemsize == 16 and KEY_MATERIAL.itemsize == 84
 assert WALK.itemsize == 24 and ACCEPT.itemsize == 8
 assert SECRET.itemsize == 80 and INITIAL.itemsize == 32

@@ -836,15 +836,53 @@ def answer_routed(router, datagrams: Sequence[bytes], addrs: Sequence[Any], acce
     return _accept_routed(router, datagrams, accept, tokens is not None, (addrs, tokens, supported_versions))
 
 
+def serve_routed(router, datagrams: Sequence[bytes], addrs: Sequence[Any], accept, *, tokens,
+                 supported_versions: Sequence[int] = (1, 0x6B3343CF)):
+    """answer_routed for a server in Retry mode whose tokens the device also
+    validates: a Retry-mode server's whole policy for unrouted Initials
+    (asyncio/server.py:71-131) in the one fused call (_crypto.receive_serve).
+
+    Returns (records, unrouted, accepted, replies, dropped).  `tokens` is a
+    retry.RetryTokens and is required (ValueError for None: a server not in
+    Retry mode uses answer_routed).  Where answer_routed accepts every Initial
+    that carries a token and leaves tokens.validate_token to `accept`, here a
+    kernel finds each candidate's token, one AEAD-only launch opens them all
+    under the token key, and the accepting kernel compares the address and
+    cuts out the two CIDs before it accepts anything: a token that is not
+    ours, or not this address's, costs no keys, no slots and no unprotect.
+    The differences to answer_routed:
+
+    `accept` is called as accept(header, datagram_index,
+    original_destination_connection_id, retry_source_connection_id), the two
+    CIDs from the device's token record, as QuicConnection takes them
+    (server.py:125-131); it needs no AEAD call.
+    A datagram whose token fails comes back in `dropped`, [(datagram_index,
+    layout.TK_* reason)] in datagram order, and neither in `unrouted` nor in
+    `replies`: the reference drops it silently (server.py:119-120).
+
+    Two kinds of token the host's validate_token would take are refused here,
+    neither of which this server issues: a CID of more than 20 bytes
+    (TK_FORM) and a token of more than layout.TOKEN_MAX bytes (TK_LENGTH).
+    Everything else is answer_routed's, the fallbacks included: a batch that
+    goes through receive_routed comes back with nothing accepted, no replies
+    and nothing dropped."""
+    if tokens is None:
+        raise ValueError("serve_routed is a Retry-mode server's: tokens is required (answer_routed takes None)")
+    return _accept_routed(router, datagrams, accept, True, (addrs, tokens, supported_versions), True)
+
+
 _vn_only = None  # the 3-slot reply table of servers not in Retry mode (its token slot is never used)
 
 
-def _accept_routed(router, datagrams, accept, need_token: bool, answer):
-    """accept_routed (answer None) and answer_routed (answer = (addrs, tokens,
-    supported_versions)): (records, unrouted, accepted, replies)."""
+def _accept_routed(router, datagrams, accept, need_token: bool, answer, serve: bool = False):
+    """accept_routed (answer None), answer_routed (answer = (addrs, tokens,
+    supported_versions)) and serve_routed (the same, serve: the tokens are
+    validated on the device): (records, unrouted, accepted, replies), and
+    with serve also dropped."""
     datagrams = datagrams if isinstance(datagrams, list) else list(datagrams)
+    none = ([], [], []) if serve else ([], [])
     if not datagrams:
-        return [], [], [], []
+        return ([], []) + none
     conns = router.conns
     if any(c is not None and c.is_client and c.host_cids is not None for c in conns):
         raise ValueError("accept_routed is a server's: the router holds a client connection")
@@ -862,8 +900,8 @@ def _accept_routed(router, datagrams, accept, need_token: bool, answer):
         keep = min(len(cand), slots.room() // 2)
         rows, cand = rows[:keep], cand[:keep]
     if not cand:
-        return receive_routed(router, datagrams) + ([], [])
-    sent = None
+        return receive_routed(router, datagrams) + none
+    sent = tokrec = None
     if answer is not None:
         from .retry import RetryTokens, packed_address
 
@@ -884,6 +922,9 @@ def _accept_routed(router, datagrams, accept, need_token: bool, answer):
                      L.A_NEED_TOKEN if need_token else 0)
         if answer is None:
             route_b, _, longs, found = _crypto.receive_accept(*call_args)
+        elif serve:
+            route_b, _, longs, found, sent, tokrec_b = _crypto.receive_serve(*call_args, *reply_args)
+            tokrec = np.frombuffer(tokrec_b, dtype=L.TOKEN_REC)
         else:
             route_b, _, longs, found, sent = _crypto.receive_accept_reply(*call_args, *reply_args)
         route = np.frombuffer(route_b, dtype=L.ROUTE)
@@ -903,7 +944,13 @@ def _accept_routed(router, datagrams, accept, need_token: bool, answer):
             if dcid not in by_dcid:
                 header = _long_header(data, 0, QuicPacketType.INITIAL, int(w["version"]), int(w["len"]),
                                       int(w["dcid_len"]), int(w["scid_len"]), int(w["token_len"]))
-                conn = by_dcid[dcid] = accept(header, i)
+                if tokrec is None:
+                    conn = accept(header, i)
+                else:
+                    t = tokrec[a]
+                    conn = accept(header, i, t["odcid"][:int(t["odcid_len"])].tobytes(),
+                                  t["rscid"][:int(t["rscid_len"])].tobytes())
+                by_dcid[dcid] = conn
                 if conn is not None:
                     pair = (conn.cryptos_initial or {}).get(header.version)
                     space = conn.spaces.get(Epoch.INITIAL)
@@ -923,7 +970,11 @@ def _accept_routed(router, datagrams, accept, need_token: bool, answer):
     finally:
         slots.give_back(taken)
     if host:
-        return receive_routed(router, datagrams) + ([], [])
+        return receive_routed(router, datagrams) + none
+    dropped = []
+    if tokrec is not None:
+        bad = np.flatnonzero(acc["status"] == L.ACC_BAD_TOKEN).tolist()
+        dropped = [(cand[a], int(tokrec["status"][a])) for a in bad]
     replies = []
     if sent is not None:
         rrec = np.frombuffer(sent[1], dtype=L.REPLY)
@@ -941,8 +992,9 @@ def _accept_routed(router, datagrams, accept, need_token: bool, answer):
     here[np.asarray(list(joined), np.int64)] = True
     gone = here.copy()
     gone[np.asarray([i for i, _ in replies], np.int64)] = True  # answered: server.py returns after sendto
+    gone[np.asarray([i for i, _ in dropped], np.int64)] = True  # a token that failed: dropped silently (:119-120)
     unrouted = [(int(i), int(cls[i])) for i in np.flatnonzero(~gone)]
     recs = _routed_long(router.conns, datagrams, cid_len, np.flatnonzero(here).tolist(), cls, rconn, longs, slots,
                         joined)
     assert recs is not None  # _host_walk_needed ruled its reasons out
-    return recs, unrouted, [(i, c) for i, c, _, _ in new], replies
+    return (recs, unrouted, [(i, c) for i, c, _, _ in new], replies) + ((dropped,) if serve else ())

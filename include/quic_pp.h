@@ -537,6 +537,100 @@ int qpp_route_accept(const uint64_t *d_off, const uint32_t *d_len, uint32_t n, c
  * library loaded).  Diagnostic: a batch without candidates makes none. */
 uint64_t qpp_route_accept_launches(void);
 
+/* qpp_route_token and qpp_route_accept_tokens: the Retry token a client sends
+ * back in its second Initial, validated on the device before anything is
+ * derived, installed or unprotected for it -- what the reference's server does
+ * per datagram with validate_token before it creates a connection
+ * (asyncio/server.py:112-120).  The token format is this server's own
+ * (aioquic_amd/retry.py): counter (8 bytes, big-endian) | AES-128-GCM(P, aad =
+ * counter, pn = counter) under slot 2 of the reply key table (qpp_route_reply),
+ * with P the buffer of QuicRetryTokenHandler.create_token (quic/retry.py:25-28):
+ * three one-byte-length opaques, the encoded address, the original DCID and
+ * the Retry's source CID.  Three steps on one stream, after qpp_route and
+ * qpp_route_walk and over their arrays:
+ *   1. qpp_route_token: one lane per candidate of d_acc_row[n_acc] (as
+ *      qpp_route_accept names them).  A lane whose candidate passes tests 1-6
+ *      of qpp_route_accept with QPP_A_NEED_TOKEN set looks for the token of
+ *      packet 0: with dl / sl / T the record's DCID, SCID and token lengths,
+ *      QPP_TOKEN_MIN <= T <= QPP_TOKEN_MAX (else QPP_TK_LENGTH), then dl, sl <=
+ *      20, 7 + dl + sl <= d_len[i], bytes 5 and 6 + dl of the datagram are dl
+ *      and sl, the varint at 7 + dl + sl (any of its encodings) fits, equals T,
+ *      and the T bytes after it end at or before d_len[i] (else QPP_TK_BOUNDS);
+ *      every bound is held against d_len, not the record.  Then d_tokdesc[a] =
+ *      {in_off = d_off[i] + the token's offset, out_off = a * QPP_TOKEN_STRIDE,
+ *      len = T, hdr_len = 8, QPP_F_NO_HP, pn = the token's first 8 bytes
+ *      big-endian, slot 2, rsv 0} and d_tokrec[a] = {QPP_TK_OK, zeros}.  Any
+ *      other candidate gets the inert descriptor {in_off = d_off[i] (0 without
+ *      a datagram), out_off = a * QPP_TOKEN_STRIDE, len 0, hdr_len 0,
+ *      QPP_F_NO_HP, pn 0, QPP_SLOT_NONE} and {QPP_TK_NONE (no token test is
+ *      due), QPP_TK_LENGTH or QPP_TK_BOUNDS, zeros}: its token is never
+ *      decrypted.  Both records are written whole for every candidate.
+ *   2. qpp_unprotect(reply_kt, d_tokdesc, n_acc, d_in, d_tok, d_tokres): d_tok
+ *      holds QPP_TOKEN_STRIDE bytes per candidate, zeroed by the caller; an
+ *      opened token leaves [counter | P] at a * 128, 8 + |P| <= 112.  The
+ *      datagram buffer is only read: a token is part of its Initial's AAD.
+ *   3. qpp_route_accept_tokens: qpp_route_accept with three more inputs
+ *      (d_addr[20 n_acc] as qpp_route_reply takes it, d_tok, d_tokres) and
+ *      d_tokrec, read and rewritten.  Tests 1-6 run unchanged; a candidate that
+ *      passes them with QPP_A_NEED_TOKEN set then gets the token's verdict: its
+ *      preliminary status if that is not QPP_TK_OK (QPP_TK_NONE included: a
+ *      token nobody examined is not accepted); QPP_TK_AUTH unless
+ *      d_tokres[a].status is QPP_S_OK, and no opened byte is read then; the
+ *      three opaques parsed as validate_token does, trailing bytes allowed, a
+ *      field that runs past the end or a CID field of more than 20 bytes
+ *      QPP_TK_FORM; field 0 against d_addr[20a] = [alen | packed IP | port],
+ *      in length and bytes (an alen that is neither 6 nor 18 matches nothing),
+ *      QPP_TK_ADDR.  QPP_TK_OK: d_tokrec[a] = {QPP_TK_OK,
+ *      the two CIDs}, and the candidate is accepted as by qpp_route_accept.
+ *      Otherwise d_tokrec[a] = {verdict, zeros} and d_acc[a].status =
+ *      QPP_ACC_BAD_TOKEN, written as any rejection is: d_ini[a] names no slot
+ *      and no CID, desc = QPP_DESC_NONE, d_desc is left alone, so no keys are
+ *      installed and nothing is unprotected.  A candidate that does not reach
+ *      the token test gets {QPP_TK_NONE, zeros}.
+ * Two deliberate divergences from the host's validate_token, neither of a
+ * token this server issues (its largest is 8 + 19 + 21 + 21 + 16 = 85 bytes): a
+ * CID field of more than 20 bytes is QPP_TK_FORM where the host returns it, and
+ * a token of more than QPP_TOKEN_MAX bytes is QPP_TK_LENGTH where the host
+ * would open one sealed with trailing bytes.
+ * QPP_E_ARG: a NULL array with n_acc > 0, an accept_flags bit other than
+ * QPP_A_NEED_TOKEN, n_acc > 2^24.  n_acc == 0 returns QPP_OK and launches
+ * nothing. */
+#define QPP_TOKEN_STRIDE 128
+#define QPP_TOKEN_MIN 27    /* 8 + 3 + 16: the bound validate_token has */
+#define QPP_TOKEN_MAX 128
+#define QPP_ACC_BAD_TOKEN 7 /* from qpp_route_accept_tokens only: dropped silently (server.py:119-120) */
+#define QPP_TK_OK 0
+#define QPP_TK_NONE 1       /* no token test was due for this candidate */
+#define QPP_TK_LENGTH 2     /* a token shorter than QPP_TOKEN_MIN or longer than QPP_TOKEN_MAX */
+#define QPP_TK_BOUNDS 3     /* the walk record's lengths do not fit the datagram's bytes */
+#define QPP_TK_AUTH 4       /* the token does not open under the token key */
+#define QPP_TK_FORM 5       /* a field runs past the plaintext's end, or a CID field of more than 20 bytes */
+#define QPP_TK_ADDR 6       /* sealed for another address */
+typedef struct qpp_token_rec {
+    uint8_t status;      /* QPP_TK_* */
+    uint8_t odcid_len;   /* with QPP_TK_OK: the original DCID (the first flight's) */
+    uint8_t rscid_len;   /*                 and the Retry's source CID */
+    uint8_t rsv;
+    uint8_t odcid[20];
+    uint8_t rscid[20];
+    uint8_t rsv2[4];
+} qpp_token_rec;         /* 48 bytes */
+int qpp_route_token(const uint64_t *d_off, const uint32_t *d_len, uint32_t n, const uint8_t *d_in,
+                    const qpp_route_rec *d_route, const uint32_t *d_long_idx, uint32_t n_long,
+                    const qpp_walk_rec *d_walk, const uint32_t *d_walk_n, const uint32_t *d_acc_row, uint32_t n_acc,
+                    uint32_t accept_flags, qpp_desc *d_tokdesc, qpp_token_rec *d_tokrec, void *stream);
+/* qpp_route_token launches of the locating kernel (process-wide, since the
+ * library loaded).  Diagnostic: a call without candidates makes none. */
+uint64_t qpp_route_token_launches(void);
+/* Counted by qpp_route_accept_launches, as the accepting kernel it is. */
+int qpp_route_accept_tokens(const uint64_t *d_off, const uint32_t *d_len, uint32_t n, const uint8_t *d_in,
+                            const qpp_route_rec *d_route, const uint32_t *d_long_idx, uint32_t n_long,
+                            const qpp_walk_rec *d_walk, const uint32_t *d_walk_n, const uint32_t *d_acc_row,
+                            const uint32_t *d_acc_slot, uint32_t n_acc, uint32_t accept_flags, uint16_t desc_flags,
+                            const uint8_t *d_addr, const uint8_t *d_tok, const qpp_result *d_tokres,
+                            qpp_initial *d_ini, qpp_desc *d_desc, qpp_accept_rec *d_acc, qpp_token_rec *d_tokrec,
+                            void *stream);
+
 /* qpp_route_reply: the packets a server sends instead of accepting, for the
  * two verdicts of qpp_route_accept after which the reference's server sends
  * something and drops the datagram (asyncio/server.py:71-111): a Version
@@ -810,6 +904,34 @@ int qpp_session_accept_reply_unprotect(qpp_session *s, qpp_keytab *kt, const qpp
                                        qpp_result *res, qpp_walk_rec *walk_out, uint32_t *walk_n_out,
                                        qpp_accept_rec *acc_out, qpp_key_material *km_out, uint8_t *secrets_out,
                                        uint8_t *reply_out, qpp_reply_rec *reply_rec_out);
+/* qpp_session_accept_reply_unprotect for a server in Retry mode that also
+ * validates the tokens that come back (asyncio/server.py:112-120;
+ * quic/retry.py): the three steps of qpp_route_token run ahead of the
+ * accepting kernel.  The sequence on the one stream is the routing kernel, the
+ * walking kernel, a memset of the token scratch, the locating kernel,
+ * qpp_unprotect(reply_kt, ...) over the n_acc token descriptors from the
+ * datagram buffer (read only) into the token scratch, the accepting kernel
+ * with the verdicts, the assembling kernel, the derivation, the batch's
+ * unprotect and the two reply protects.  A QPP_ACC_BAD_TOKEN candidate gets
+ * no keys, no slot, no unprotect and no reply.  tokrec_out[n_acc] receives the
+ * qpp_token_rec records in the same download as the accept records; the token
+ * descriptors, the opened tokens and their results never leave the device.
+ * Checked on the host before anything is launched or noted, besides what the
+ * reply form checks: QPP_A_NEED_TOKEN in accept_flags, QPP_RP_RETRY in
+ * reply_flags, reply_kt given with capacity >= 3, and with n_acc > 0 addr and
+ * tokrec_out given.  A violation is QPP_E_ARG and nothing is touched. */
+int qpp_session_serve_unprotect(qpp_session *s, qpp_keytab *kt, const qpp_cidmap *m, uint32_t cid_len,
+                                const uint64_t *off, const uint32_t *len, uint32_t n, const uint8_t *in,
+                                size_t in_len, const uint32_t *long_idx, uint32_t n_long,
+                                const uint32_t *conn_slot, const uint64_t *conn_expected, uint32_t n_conn,
+                                uint16_t desc_flags, const uint32_t *acc_row, const uint32_t *acc_slot,
+                                uint32_t n_acc, uint32_t accept_flags, const qpp_keytab *reply_kt,
+                                const uint8_t *addr, const uint8_t *rnd, uint64_t token_ctr,
+                                const uint32_t *versions, uint32_t n_versions, uint32_t reply_flags, uint8_t *out,
+                                size_t out_len, qpp_desc *desc_out, qpp_route_rec *route_out, qpp_result *res,
+                                qpp_walk_rec *walk_out, uint32_t *walk_n_out, qpp_accept_rec *acc_out,
+                                qpp_key_material *km_out, uint8_t *secrets_out, uint8_t *reply_out,
+                                qpp_reply_rec *reply_rec_out, qpp_token_rec *tokrec_out);
 /* The session's own pinned staging buffers, sized for at least `bytes` of
  * input and of output and n packets; valid until the next call on the
  * session.  A caller that assembles its input straight into *h_in and passes
