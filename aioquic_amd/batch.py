@@ -74,6 +74,18 @@ class PacketEngine:
         km = self.table.derive(np.ascontiguousarray(secrets).tobytes())
         return np.frombuffer(km, dtype=L.KEY_MATERIAL).copy()
 
+    def derive_next_keys(self, records: np.ndarray):
+        """Batched next_key_phase on the device (qpp_keytab_derive_next):
+        `records` are layout.NEXT_PHASE records.  Returns (km, secrets): the
+        KEY_MATERIAL of every record's next phase (the record's own
+        header-protection key kept) and the updated secrets, (n, 64) uint8,
+        zero past the hash length.  Records given SLOT_NONE are returned but
+        not installed."""
+        assert records.dtype == L.NEXT_PHASE
+        km, sec = self.table.derive_next(np.ascontiguousarray(records).tobytes())
+        return (np.frombuffer(km, dtype=L.KEY_MATERIAL).copy(),
+                np.frombuffer(sec, dtype=np.uint8).reshape(len(records), 64).copy())
+
     def derive_initial_keys(self, records: np.ndarray):
         """Batched CryptoPair.setup_initial on the device
         (qpp_keytab_derive_initial): `records` are layout.INITIAL records.

@@ -38,6 +38,7 @@ step (quic/connection.py:905-947, CryptoPair.decrypt_packet, crypto.py:184-192).
 
 from __future__ import annotations
 
+import struct
 import threading
 import weakref
 from typing import Optional, Union
@@ -46,11 +47,12 @@ import numpy as np
 
 from . import crypto as crypto_mod
 from . import layout as L
-from ._crypto import CryptoError, KeyTable, protect_list, unprotect_list, unprotect_walk, walk_results
+from ._crypto import CryptoError, KeyTable, aead_deferred, protect_list, unprotect_list, unprotect_walk, walk_results
 from .crypto import CryptoContext, CryptoPair, KeyUnavailableError, next_key_phase
 from .packet import decode_packet_number
 
-__all__ = ["SendBatch", "ReceiveBatch", "KeySlots", "setup_initial_batch", "ReservedBitsError",
+__all__ = ["SendBatch", "ReceiveBatch", "KeySlots", "setup_initial_batch", "setup_next_phase_batch",
+           "update_keys_batch", "ReservedBitsError",
            "ConnectionClosedError"]
 
 # host-side statuses of the C receive walks (csrc/qpp_rxwalk.h WALK_S_*)
@@ -359,6 +361,115 @@ def _install_initial(slots: KeySlots, pairs, built, versions) -> None:
             ctx._setup_cb("tls")
 
 
+# ----------------------------------------------------------- key updates --
+
+# one qpp_next_phase (layout.NEXT_PHASE) by struct; "s" zero-pads secret and hp
+_NEXT_REC = struct.Struct("<IBBBB64s32s")
+assert _NEXT_REC.size == L.NEXT_PHASE.itemsize
+_SUITE_INDEX = {
+    crypto_mod.CipherSuite.AES_128_GCM_SHA256: L.AES_128_GCM,
+    crypto_mod.CipherSuite.AES_256_GCM_SHA384: L.AES_256_GCM,
+    crypto_mod.CipherSuite.CHACHA20_POLY1305_SHA256: L.CHACHA20_POLY1305,
+}
+
+
+def _derive_next(table: KeyTable, ctxs: list, slot_of: list) -> list:
+    """next_key_phase for every context of `ctxs` in ONE device call
+    (KeyTable.derive_next): context i's next phase is installed in slot_of[i]
+    under the context's own header-protection key, or only derived where that
+    is L.SLOT_NONE.  Returns the next contexts: key phase flipped, cipher suite
+    and version copied, the updated secret, an AEAD whose own device table
+    waits for a first use that the batched paths never make, and the current
+    context's HP object, which a key update keeps.  No callback fires."""
+    recs = []
+    for ctx, slot in zip(ctxs, slot_of):
+        suite = _SUITE_INDEX[ctx.cipher_suite]
+        recs.append(_NEXT_REC.pack(slot, suite, 1 - int(bool(ctx.key_phase)),
+                                   L.DERIVE_V2 if ctx.version == crypto_mod.QuicProtocolVersion.VERSION_2 else 0,
+                                   len(ctx.secret), ctx.secret, ctx.hp._material()[1]))
+    km_b, secrets = table.derive_next(b"".join(recs))
+    km = np.frombuffer(km_b, dtype=L.KEY_MATERIAL)
+    keys, ivs = km["key"], km["iv"]
+    out = []
+    for i, ctx in enumerate(ctxs):
+        suite = crypto_mod._SUITES[ctx.cipher_suite]
+        hl = 48 if ctx.cipher_suite == crypto_mod.CipherSuite.AES_256_GCM_SHA384 else 32
+        nxt = CryptoContext(key_phase=1 - int(bool(ctx.key_phase)))
+        nxt.cipher_suite, nxt.version = ctx.cipher_suite, ctx.version
+        nxt.secret = secrets[64 * i: 64 * i + hl]
+        nxt.aead = aead_deferred(suite.aead_name, keys[i, : suite.key_len].tobytes(), ivs[i].tobytes())
+        nxt.hp = ctx.hp
+        out.append(nxt)
+    return out
+
+
+def setup_next_phase_batch(contexts, slots: Optional[KeySlots] = None) -> None:
+    """crypto.cached_next_phase for many contexts: every keyed CryptoContext
+    of `contexts` that has no cached next phase gets one, from ONE device call
+    (KeyTable.derive_next) that also installs the next keys, under the
+    contexts' unchanged header-protection keys, in slots of `slots` (default:
+    this thread's default_slots()) bound to (next.aead, ctx.hp,
+    next.key_phase), where the assign() of a later batch finds them.  Contexts
+    that have a cached next phase are skipped; an empty list is a no-op.  The
+    table is never cleared and refilled for them: OverflowError when it has no
+    room for them all, with no state moved."""
+    slots = slots if slots is not None else default_slots()
+    seen: set = set()
+    todo = []
+    for ctx in contexts:
+        if ctx.aead is not None and ctx._next is None and id(ctx) not in seen:
+            seen.add(id(ctx))
+            todo.append(ctx)
+    if not todo:
+        return
+    if slots.room() < len(todo):
+        raise OverflowError("key table full")
+    taken = slots.reserve(len(todo))
+    nexts = _derive_next(slots.table, todo, taken)
+    slots.adopt(taken, [(nxt.aead, ctx.hp, nxt.key_phase) for ctx, nxt in zip(todo, nexts)])
+    for ctx, nxt in zip(todo, nexts):
+        ctx._next = nxt
+
+
+def update_keys_batch(pairs, trigger: str, slots: Optional[KeySlots] = None) -> None:
+    """CryptoPair._update_key(trigger) for many pairs: ONE device call
+    (KeyTable.derive_next) derives the next phase of every direction that has
+    no cached one -- the send directions as derive-only records, a receive
+    direction installed in a slot of `slots` (default: this thread's
+    default_slots()) when the table has room, derive-only otherwise -- and
+    then apply_key_phase runs on recv and then send of each pair, pairs in
+    order: the callbacks of _update_key in its order.  The AEADs the contexts
+    let go of reach every key table as one release()."""
+    slots = slots if slots is not None else default_slots()
+    pairs = list(pairs)
+    if not pairs:
+        return
+    need = []
+    seen: set = set()
+    for pair in pairs:
+        for ctx in (pair.recv, pair.send):
+            if ctx._next is None and id(ctx) not in seen:
+                seen.add(id(ctx))
+                need.append((ctx, ctx is pair.recv))
+    made: dict = {}
+    if need:
+        n_recv = sum(1 for _, is_recv in need if is_recv)
+        taken = slots.reserve(n_recv) if n_recv and slots.room() >= n_recv else []
+        it = iter(taken)
+        slot_of = [next(it, L.SLOT_NONE) if is_recv else L.SLOT_NONE for _, is_recv in need]
+        ctxs = [ctx for ctx, _ in need]
+        nexts = _derive_next(slots.table, ctxs, slot_of)
+        held = [(s, ctx, nxt) for s, ctx, nxt in zip(slot_of, ctxs, nexts) if s != L.SLOT_NONE]
+        slots.adopt([s for s, _, _ in held], [(nxt.aead, ctx.hp, nxt.key_phase) for _, ctx, nxt in held])
+        made = {id(ctx): nxt for ctx, nxt in zip(ctxs, nexts)}
+    with crypto_mod._releases_together():
+        for pair in pairs:
+            for ctx in (pair.recv, pair.send):
+                nxt = ctx._next if ctx._next is not None else made[id(ctx)]
+                crypto_mod.apply_key_phase(ctx, nxt, trigger=trigger)
+            pair._update_key_requested = False
+
+
 def _raise_status(status: int) -> Exception:
     if status == _S_RESERVED:
         return ReservedBitsError("Reserved bits must be zero")
@@ -492,8 +603,11 @@ def _signed_trunc(pn: int, pn_len: int) -> int:
 class ReceiveBatch:
     """Batched CryptoPair.decrypt_packet for QuicConnection.receive_datagram."""
 
-    def __init__(self, slots: Optional[KeySlots] = None, capacity: int = 1024) -> None:
+    def __init__(self, slots: Optional[KeySlots] = None, capacity: int = 1024, device_keys: bool = False) -> None:
         self.slots = slots or KeySlots(capacity)
+        # the next key phases run() needs come from the batched device calls
+        # (_derive_next, update_keys_batch) instead of next_key_phase / _update_key
+        self.device_keys = bool(device_keys)
         self._pairs: list = []
         self._packets: list = []
         self._offs: list = []
@@ -747,6 +861,11 @@ class ReceiveBatch:
             if flip:
                 nxt_keys: dict = {}
                 triples = []
+                if self.device_keys:
+                    # every flipped pair's next phase from one derive-only call
+                    first = {id(cur[0]): pairs[i].recv for i, cur in reversed(flip)}
+                    made = _derive_next(self.slots.table, list(first.values()), [L.SLOT_NONE] * len(first))
+                    nxt_keys = {k: (nxt.aead, ctx.hp, nxt.key_phase) for (k, ctx), nxt in zip(first.items(), made)}
                 for i, cur in flip:
                     k = id(cur[0])
                     if k not in nxt_keys:
@@ -781,8 +900,11 @@ class ReceiveBatch:
                 outcome[i] = o
             for space, v in exp.values():
                 space.expected_packet_number = v
-            for pair in rolls:
-                pair._update_key("remote_update")
+            if self.device_keys:
+                update_keys_batch(rolls, "remote_update", self.slots)
+            else:
+                for pair in rolls:
+                    pair._update_key("remote_update")
             if flip:
                 # the retry keys were this round's own: a roll builds the
                 # pair's next phase afresh

@@ -20,6 +20,8 @@ module in its place.  The design underneath differs:
 from __future__ import annotations
 
 import struct
+import threading
+from contextlib import contextmanager
 from dataclasses import dataclass
 from typing import Callable, Dict, Optional, Tuple
 
@@ -62,9 +64,35 @@ def NoCallback(trigger: str) -> None:
 _KEY_RELEASE_HOOKS: list = []
 
 
+_release_scope = threading.local()
+
+
 def _release(*objs) -> None:
+    held = getattr(_release_scope, "held", None)
+    if held is not None:
+        held.extend(objs)  # inside _releases_together(): handed over at its end
+        return
     for hook in _KEY_RELEASE_HOOKS:
         hook(*objs)
+
+
+@contextmanager
+def _releases_together():
+    """What this thread's contexts let go of inside the block reaches the
+    hooks as one call at its end (batch_io.update_keys_batch: one clear launch
+    per key table for a whole batch of key updates, not one per AEAD)."""
+    if getattr(_release_scope, "held", None) is not None:
+        yield  # nested: the outer block hands over
+        return
+    held: list = []
+    _release_scope.held = held
+    try:
+        yield
+    finally:
+        _release_scope.held = None
+        if held:
+            for hook in _KEY_RELEASE_HOOKS:
+                hook(*held)
 
 
 class KeyUnavailableError(CryptoError):

@@ -17,7 +17,8 @@
  * Batch API (pointers are ints: device pointers for the device forms, host
  * pointers for the *_into forms; the caller keeps the memory alive):
  *   KeyTable(capacity) .set(materials) .derive(secrets) .derive_initial(records)
- *                      .derive_trace(enable) .clear(slots) .capacity
+ *                      .derive_next(records) .derive_trace(enable) .clear(slots) .capacity
+ *   aead_deferred(cipher_name, key, iv)             an AEAD whose device table waits for its first use
  *   Plan(capacity)                                  device scratch of the bucketing step
  *   protect(table, desc_ptr, n, in_ptr, out_ptr, res_ptr, stream[, plan])   -> None
  *   unprotect(...)                                                          -> None
@@ -190,7 +191,15 @@ static void par_copy(uint8_t **dst, const uint8_t **src, const size_t *len, size
 /* ------------------------------------------------------------ key slot -- */
 
 /* A single-slot device key table, created on first use.  The slot is
- * read-only after creation, so objects may be used from any thread. */
+ * read-only after creation, so objects may be used from any thread.
+ * First use cannot create it twice for one object: every caller of
+ * oneslot_ready holds the GIL, and nothing between the NULL test and the
+ * point where kt holds a table with its key installed releases it -- session(),
+ * qpp_keytab_create and qpp_session_set_keys are plain C calls into the
+ * library (none is wrapped in Py_BEGIN_ALLOW_THREADS, none calls back into
+ * Python), so a second thread's first use starts after the first one's has
+ * ended and finds kt set.  The extension is built for the limited API, which
+ * a free-threaded interpreter does not load. */
 typedef struct {
     qpp_key_material km;
     qpp_keytab *kt;
@@ -226,7 +235,9 @@ typedef struct {
     OneSlot s;
 } AEADObject;
 
-static int AEAD_init(AEADObject *self, PyObject *args, PyObject *kwargs)
+/* The constructor's argument checks and the key material, without the device
+ * table: AEAD(...) creates that at once, aead_deferred(...) at first use. */
+static int aead_fill(AEADObject *self, PyObject *args)
 {
     const char *name;
     const unsigned char *key, *iv;
@@ -254,7 +265,30 @@ static int AEAD_init(AEADObject *self, PyObject *args, PyObject *kwargs)
     oneslot_reset(&self->s, suite);
     memcpy(self->s.km.key, key, (size_t)key_len);
     memcpy(self->s.km.iv, iv, (size_t)iv_len); /* short iv: zero padded, as the reference */
+    return 0;
+}
+
+static int AEAD_init(AEADObject *self, PyObject *args, PyObject *kwargs)
+{
+    if (aead_fill(self, args) < 0) return -1;
     return oneslot_ready(&self->s);
+}
+
+/* aead_deferred(cipher_name, key, iv) -> an AEAD whose one-slot device table
+ * is created by its first encrypt / decrypt (aead_run's oneslot_ready), not
+ * here: the batched key-update path builds one per connection and most are
+ * only ever read through _material().  The same argument checks and errors as
+ * AEAD(...); without a device the RuntimeError comes at first use instead. */
+static PyObject *py_aead_deferred(PyObject *m, PyObject *args)
+{
+    allocfunc alloc = (allocfunc)PyType_GetSlot((PyTypeObject *)g_aead_type, Py_tp_alloc);
+    AEADObject *self = (AEADObject *)alloc((PyTypeObject *)g_aead_type, 0);  /* zeroed: s.kt NULL */
+    if (!self) return NULL;
+    if (aead_fill(self, args) < 0) {
+        Py_DECREF(self);
+        return NULL;
+    }
+    return (PyObject *)self;
 }
 
 static void AEAD_dealloc(AEADObject *self)
@@ -590,8 +624,49 @@ static PyObject *KT_derive_initial(KeyTableObject *self, PyObject *args)
     return ret;
 }
 
+/* KeyTable.derive_next(records[, stream]) -> (key material, secrets): batched
+ * next_key_phase (qpp_keytab_derive_next); records = whole qpp_next_phase
+ * records; one qpp_key_material and one 64-byte zero-padded secret per record. */
+static PyObject *KT_derive_next(KeyTableObject *self, PyObject *args)
+{
+    const char *b;
+    Py_ssize_t len;
+    unsigned long long stream = 0;
+    if (!PyArg_ParseTuple(args, "y#|K", &b, &len, &stream)) return NULL;
+    if (len % (Py_ssize_t)sizeof(qpp_next_phase) || len / (Py_ssize_t)sizeof(qpp_next_phase) > (1 << 24)) {
+        PyErr_SetString(PyExc_ValueError, "records must be a whole number (up to 2^24) of 104-byte records");
+        return NULL;
+    }
+    uint32_t n = (uint32_t)(len / (Py_ssize_t)sizeof(qpp_next_phase));
+    PyObject *km = PyBytes_FromStringAndSize(NULL, (Py_ssize_t)n * (Py_ssize_t)sizeof(qpp_key_material));
+    PyObject *sec = PyBytes_FromStringAndSize(NULL, (Py_ssize_t)n * 64);
+    if (!km || !sec) {
+        Py_XDECREF(km);
+        Py_XDECREF(sec);
+        return NULL;
+    }
+    qpp_key_material *out = (qpp_key_material *)PyBytes_AsString(km);
+    uint8_t *sout = (uint8_t *)PyBytes_AsString(sec);
+    int rc;
+    Py_BEGIN_ALLOW_THREADS
+    rc = qpp_keytab_derive_next(self->kt, (const qpp_next_phase *)b, n, out, sout, as_ptr(stream));
+    Py_END_ALLOW_THREADS
+    if (rc == QPP_E_ARG)
+        PyErr_SetString(PyExc_ValueError,
+                        "bad next-phase record (slot out of range, unknown suite, secret length, key phase or flag)");
+    if (rc == QPP_E_ARG || check_rc(rc) < 0) {
+        Py_DECREF(km);
+        Py_DECREF(sec);
+        return NULL;
+    }
+    PyObject *ret = PyTuple_Pack(2, km, sec);
+    Py_DECREF(km);
+    Py_DECREF(sec);
+    return ret;
+}
+
 /* KeyTable.derive_trace(enable=-1) -> (derive_ms, setup_ms) of the last timed
- * derive_initial call (qpp_keytab_derive_trace). */
+ * derive_initial or derive_next call (qpp_keytab_derive_trace). */
 static PyObject *KT_derive_trace(KeyTableObject *self, PyObject *args)
 {
     int enable = -1;
@@ -625,8 +700,10 @@ static PyMethodDef KT_methods[] = {
     {"derive", (PyCFunction)KT_derive, METH_VARARGS, "derive(secrets, stream=0) -> key material"},
     {"derive_initial", (PyCFunction)KT_derive_initial, METH_VARARGS,
      "derive_initial(records, stream=0) -> (key material, secrets)"},
+    {"derive_next", (PyCFunction)KT_derive_next, METH_VARARGS,
+     "derive_next(records, stream=0) -> (key material, secrets)"},
     {"derive_trace", (PyCFunction)KT_derive_trace, METH_VARARGS,
-     "derive_trace(enable=-1) -> (derive_ms, setup_ms) of the last timed derive_initial"},
+     "derive_trace(enable=-1) -> (derive_ms, setup_ms) of the last timed derive_initial / derive_next"},
     {NULL},
 };
 
@@ -2919,6 +2996,8 @@ static PyObject *py_decode_pn_signed(PyObject *m, PyObject *args)
 }
 
 static PyMethodDef module_methods[] = {
+    {"aead_deferred", py_aead_deferred, METH_VARARGS,
+     "aead_deferred(cipher_name, key, iv) -> AEAD whose device key table is created at first use"},
     {"route_walk", py_route_walk, METH_VARARGS, "qpp_route_walk on device buffers"},
     {"route_walk_unprotect_host", py_route_walk_unprotect_host, METH_VARARGS,
      "qpp_session_route_walk_unprotect on host buffers"},

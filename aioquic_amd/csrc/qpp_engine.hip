@@ -27,6 +27,7 @@
 #include "qpp_gf128.h"
 #include "qpp_device.h"
 #include "qpp_hkdf.h"
+#include "qpp_next.h"
 #include "qpp_internal.h"
 #include "qpp_phase.h"
 
@@ -2706,6 +2707,41 @@ __global__ __launch_bounds__(kDeriveWG) void k_derive(const qpp_secret *__restri
     km[i] = r;
 }
 
+// Batched next_key_phase (quic/crypto.py:148-168), one lane per record: the
+// "quic ku" secret, its key and iv, and the record's own header-protection
+// key, which a key update keeps (qpp_next::lane, the same code the CPU test
+// runs).  km[i]: the key material for k_key_setup, secrets[16i, 16i + 16): the
+// updated secret, zero padded, written as whole words.  Cold path (once per
+// key phase); the byte-array HKDF of k_derive.
+constexpr int kNextWG = 64;
+
+__global__ __launch_bounds__(kNextWG) void k_derive_next(const qpp_next_phase *__restrict__ rec,
+                                                         uint32_t n,
+                                                         qpp_key_material *__restrict__ km,
+                                                         uint32_t *__restrict__ secrets)
+{
+    static_assert(sizeof(qpp_next_phase) == sizeof(qpp_next::Rec) &&
+                      offsetof(qpp_next_phase, secret) == offsetof(qpp_next::Rec, secret) &&
+                      offsetof(qpp_next_phase, hp) == offsetof(qpp_next::Rec, hp) &&
+                      sizeof(qpp_key_material) == sizeof(qpp_next::KeyMaterial) &&
+                      offsetof(qpp_key_material, hp) == offsetof(qpp_next::KeyMaterial, hp),
+                  "qpp_next.h restates the ABI records");
+    const uint32_t i = blockIdx.x * kNextWG + threadIdx.x;
+    if (i >= n) return;
+    qpp_next::Rec r;
+    memcpy(&r, rec + i, sizeof r);
+    qpp_next::KeyMaterial k;
+    uint8_t sec[qpp_next::kSecretMax];
+    qpp_next::lane(r, k, sec);
+    qpp_key_material out;
+    memcpy(&out, &k, sizeof out);
+    km[i] = out;
+    uint32_t *s = secrets + (size_t)i * (qpp_next::kSecretMax / 4);
+    for (int j = 0; j < qpp_next::kSecretMax / 4; ++j)
+        s[j] = sec[4 * j] | (uint32_t)sec[4 * j + 1] << 8 | (uint32_t)sec[4 * j + 2] << 16 |
+               (uint32_t)sec[4 * j + 3] << 24;
+}
+
 // Batched CryptoPair.setup_initial (quic/crypto.py:201-227), two lanes per
 // connection: lane 2i derives record i's "client in" keys and lane 2i + 1 its
 // "server in" keys (the chains are independent after the extract, which both
@@ -3072,6 +3108,63 @@ int qpp_keytab_derive(qpp_keytab *kt, const qpp_secret *sec, uint32_t n,
     // the secrets are caller host memory: finish before returning
     if (hipStreamSynchronize(s) != hipSuccess && rc == QPP_OK) rc = QPP_E_HIP;
     (void)hipFree(d_sec);
+    (void)hipGetLastError();
+    return rc;
+}
+
+int qpp_keytab_derive_next(qpp_keytab *kt, const qpp_next_phase *rec, uint32_t n,
+                           qpp_key_material *km_out, uint8_t *secrets_out, void *stream)
+{
+    if (!kt || (!rec && n)) return QPP_E_ARG;
+    if (n == 0) return QPP_OK;
+    if (n > (1u << 24)) return QPP_E_ARG;
+    for (uint32_t i = 0; i < n; ++i) {
+        qpp_next::Rec r;
+        memcpy(&r, rec + i, sizeof r);
+        if (!qpp_next::check(r, kt->cap)) return QPP_E_ARG;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (n > kt->km_cap) {
+        if (kt->d_km) HIPCHK(hipFree(kt->d_km));
+        kt->d_km = NULL;
+        kt->km_cap = 0;
+        HIPCHK(hipMalloc(&kt->d_km, (size_t)n * sizeof(qpp_key_material)));
+        kt->km_cap = n;
+    }
+    // one temporary: the records, then the n secrets
+    const size_t rec_bytes = (size_t)n * sizeof(qpp_next_phase), sec_bytes = (size_t)n * 64;
+    uint8_t *d_tmp = NULL;
+    HIPCHK(hipMalloc(&d_tmp, rec_bytes + sec_bytes));
+    int rc = QPP_OK;
+    if (hipMemcpyAsync(d_tmp, rec, rec_bytes, hipMemcpyHostToDevice, s) != hipSuccess) {
+        rc = QPP_E_HIP;
+    } else {
+        for (uint32_t i = 0; i < n; ++i)
+            if (rec[i].slot != QPP_SLOT_NONE) keytab_note(kt, rec[i].slot, rec[i].suite);
+        const bool timed = kt->trace;
+        if (timed) (void)hipEventRecord(kt->tev[0], s);
+        hipLaunchKernelGGL(k_derive_next, dim3((n + kNextWG - 1) / kNextWG), dim3(kNextWG), 0, s,
+                           (const qpp_next_phase *)d_tmp, n, kt->d_km, (uint32_t *)(d_tmp + rec_bytes));
+        if (timed) (void)hipEventRecord(kt->tev[1], s);
+        // derive-only records carry QPP_SLOT_NONE >= cap: their workgroups return at once
+        hipLaunchKernelGGL(k_key_setup, dim3(n), dim3(kSetupWG), 0, s, kt->d_slots, kt->d_gtab, kt->cap,
+                           kt->d_km, n);
+        if (timed) (void)hipEventRecord(kt->tev[2], s);
+        if (hipGetLastError() != hipSuccess) rc = QPP_E_HIP;
+        else if (km_out && hipMemcpyAsync(km_out, kt->d_km, (size_t)n * sizeof(qpp_key_material),
+                                          hipMemcpyDeviceToHost, s) != hipSuccess)
+            rc = QPP_E_HIP;
+        else if (secrets_out && hipMemcpyAsync(secrets_out, d_tmp + rec_bytes, sec_bytes,
+                                               hipMemcpyDeviceToHost, s) != hipSuccess)
+            rc = QPP_E_HIP;
+    }
+    // the records and the outputs are caller host memory: finish before returning
+    if (hipStreamSynchronize(s) != hipSuccess && rc == QPP_OK) rc = QPP_E_HIP;
+    if (kt->trace && rc == QPP_OK &&
+        (hipEventElapsedTime(&kt->trace_ms[0], kt->tev[0], kt->tev[1]) != hipSuccess ||
+         hipEventElapsedTime(&kt->trace_ms[1], kt->tev[1], kt->tev[2]) != hipSuccess))
+        kt->trace_ms[0] = kt->trace_ms[1] = 0;
+    (void)hipFree(d_tmp);
     (void)hipGetLastError();
     return rc;
 }

@@ -69,6 +69,20 @@ INITIAL = np.dtype(
     ]
 )
 SLOT_NONE = 0xFFFFFFFF  # QPP_SLOT_NONE: derive this direction but do not install it
+# qpp_next_phase: one context's current traffic secret and header-protection
+# key for KeyTable.derive_next, and the slot (or SLOT_NONE) of its next phase
+NEXT_PHASE = np.dtype(
+    [
+        ("slot", "<u4"),
+        ("suite", "u1"),
+        ("key_phase", "u1"),
+        ("flags", "u1"),
+        ("secret_len", "u1"),
+        ("secret", "u1", (64,)),
+        ("hp", "u1", (32,)),
+    ]
+)
+assert NEXT_PHASE.itemsize == 104
 CID_MAX = 20
 # qpp_cid_entry: one connection ID of a CidMap and the caller's connection index
 CID_ENTRY = np.dtype(
@@ -139,6 +153,25 @@ def key_material(slot: int, suite: int, key: bytes, iv: bytes, hp: bytes, key_ph
     rec["key_phase"] = key_phase
     rec["iv"][0, : len(iv)] = np.frombuffer(iv, dtype=np.uint8)
     rec["key"][0, : len(key)] = np.frombuffer(key, dtype=np.uint8)
+    rec["hp"][0, : len(hp)] = np.frombuffer(hp, dtype=np.uint8)
+    return rec
+
+
+def next_phase_record(slot: int, suite: int, secret: bytes, hp: bytes, *, key_phase: int, v2: bool = False):
+    """One qpp_next_phase: a context's current traffic secret and
+    header-protection key; `key_phase` is the next phase's bit and `slot`
+    where it is installed (SLOT_NONE: derived and returned only)."""
+    if not 1 <= len(secret) <= 64:
+        raise ValueError("secret must be 1..64 bytes")
+    if len(hp) > 32:
+        raise ValueError("header-protection key longer than 32 bytes")
+    rec = np.zeros(1, dtype=NEXT_PHASE)
+    rec["slot"] = slot
+    rec["suite"] = suite
+    rec["key_phase"] = key_phase
+    rec["flags"] = DERIVE_V2 if v2 else 0
+    rec["secret_len"] = len(secret)
+    rec["secret"][0, : len(secret)] = np.frombuffer(secret, dtype=np.uint8)
     rec["hp"][0, : len(hp)] = np.frombuffer(hp, dtype=np.uint8)
     return rec
 

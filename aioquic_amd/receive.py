@@ -44,7 +44,7 @@ from . import _crypto
 from . import layout as L
 from ._crypto import CryptoError
 from .batch_io import (ConnectionClosedError, ReceiveBatch, ReservedBitsError, _initial_directions, _install_initial,
-                       default_slots, setup_initial_batch)
+                       default_slots, setup_initial_batch, setup_next_phase_batch, update_keys_batch)
 from .buffer import Buffer
 from .crypto import KeyUnavailableError, cached_next_phase
 from .packet import (
@@ -506,6 +506,14 @@ def _routed_long(conns, datagrams, cid_len: int, idx: list, cls, rconn, longs, s
 
 def receive_routed(router, datagrams: Sequence[bytes], *,
                    next_phase: bool = False) -> Tuple[List[ReceivedPacket], List[Tuple[int, int]]]:
+    """receive_routed_keys(router, datagrams, next_phase=next_phase), which
+    documents it: the entry point as it was before the key schedule of a
+    peer's key update had a device form (its parameter list is pinned)."""
+    return receive_routed_keys(router, datagrams, next_phase=next_phase)
+
+
+def receive_routed_keys(router, datagrams: Sequence[bytes], *, next_phase: bool = False,
+                        device_keys: bool = False) -> Tuple[List[ReceivedPacket], List[Tuple[int, int]]]:
     """receive_datagrams for raw datagrams nobody has demultiplexed: the
     device routes each to its connection by connection ID (route.CidRouter,
     qpp_route), instead of the reference's per-datagram pull_quic_header and
@@ -552,19 +560,32 @@ def receive_routed(router, datagrams: Sequence[bytes], *,
     after the update still is: the reference tries it on the phase after next
     and fails).  A batch on the general path, one whose long headers reach
     known connections (_routed_long), and a key table too small for the next
-    slots beside the batch's other keys run without next slots, as by default."""
+    slots beside the batch's other keys run without next slots, as by default.
+
+    `device_keys` (looked at only with `next_phase`) takes the key schedule of
+    those updates off the host: the next phases that are not cached yet are
+    derived and installed by one device call for the whole batch
+    (batch_io.setup_next_phase_batch, after the batch's current keys are
+    assigned and only if the table has room for them; else the batch runs
+    without next slots), the rolled pairs are committed by one more
+    (batch_io.update_keys_batch), and what is deferred runs on the same two
+    calls.  No per-connection HKDF and no per-object key table is made; the
+    records, the contexts' state and the callbacks are those of `next_phase`
+    alone."""
     datagrams = datagrams if isinstance(datagrams, list) else list(datagrams)
     if not datagrams:
         return [], []
     conns = router.conns
     general = any(c is not None and c.is_client and c.host_cids is not None for c in conns)
-    slots, uspaces, sexp, arrays, _, nxt = _routed_arrays_next(router, datagrams, general, next_phase)
+    device_keys = bool(device_keys and next_phase)
+    slots, uspaces, sexp, arrays, _, nxt = _routed_arrays_next(router, datagrams, general, next_phase, device_keys)
     closed = bytes(bool(c is not None and c.closed) for c in conns)
     if nxt is None:
         route_b, walked, longs = _crypto.receive_routed(
             slots.table, router.map, router.host_cid_length, datagrams, *arrays, ReceivedPacket,
             QuicPacketType.ONE_RTT, Epoch.ONE_RTT, closed, 0 if general else 1)
-        return _routed_finish(router, datagrams, slots, uspaces, sexp, route_b, walked, longs)
+        return _routed_finish(router, datagrams, slots, uspaces, sexp, route_b, walked, longs,
+                              device_keys=device_keys)
     upairs, pnext = nxt
     route_b, walked, longs = _crypto.receive_routed_phase(
         slots.table, router.map, router.host_cid_length, datagrams, *arrays, ReceivedPacket,
@@ -575,7 +596,7 @@ def receive_routed(router, datagrams: Sequence[bytes], *,
         return receive_routed(router, datagrams)
     rolled = walked[4]
     return _routed_finish(router, datagrams, slots, uspaces, sexp, route_b, walked[:4], longs,
-                          [upairs[k] for k, f in enumerate(rolled) if f])
+                          [upairs[k] for k, f in enumerate(rolled) if f], device_keys)
 
 
 def _routed_arrays(router, datagrams: list, general: bool):
@@ -583,7 +604,7 @@ def _routed_arrays(router, datagrams: list, general: bool):
     return _routed_arrays_next(router, datagrams, general, False)[:5]
 
 
-def _routed_arrays_next(router, datagrams: list, general: bool, next_phase: bool):
+def _routed_arrays_next(router, datagrams: list, general: bool, next_phase: bool, device_keys: bool = False):
     """What the fused calls of receive_routed and accept_routed take besides
     the datagrams: every key the batch can need is given a slot here, in one
     assign().  Returns (slots, the distinct 1-RTT spaces, their expected
@@ -635,7 +656,20 @@ def _routed_arrays_next(router, datagrams: list, general: bool, next_phase: bool
         # one assign() for the whole batch: a refill must not take an earlier slot away
         rc = [upairs[k].recv for k in keyed] + [p.recv for p in xp]
         triples = [(c.aead, c.hp, c.key_phase) for c in rc]
-        if pnext is not None:
+        if pnext is not None and device_keys:
+            # the batch's current keys first, as without next slots; then the next phases, never
+            # by a refill (it would take those away): the missing ones from one device call
+            got = slots.assign(triples)
+            cur = [upairs[k].recv for k in keyed]
+            missing = [c for c in cur if c._next is None]
+            unbound = sum(1 for c in cur if c._next is not None
+                          and (id(c._next.aead), id(c.hp), int(c._next.key_phase)) not in slots._slot)
+            if slots.room() >= len(missing) + unbound:
+                setup_next_phase_batch(missing, slots)
+                pnext[keyed] = slots.assign([(c._next.aead, c.hp, c._next.key_phase) for c in cur])
+            else:
+                pnext = None
+        elif pnext is not None:
             # the next phase's AEAD key under the current HP key, with the other phase bit
             ahead = [cached_next_phase(upairs[k].recv) for k in keyed]
             try:
@@ -689,9 +723,11 @@ def _routed_arrays_next(router, datagrams: list, general: bool, next_phase: bool
         None if pnext is None else (upairs, pnext)
 
 
-def _routed_finish(router, datagrams: list, slots, uspaces, sexp, route_b, walked, longs, rolled=()):
+def _routed_finish(router, datagrams: list, slots, uspaces, sexp, route_b, walked, longs, rolled=(),
+                   device_keys: bool = False):
     """receive_routed from what its fused call returned; `rolled`: the pairs
-    whose keys a packet of the batch updated (next_phase)."""
+    whose keys a packet of the batch updated (next_phase); `device_keys`: they
+    are committed, and what is deferred runs, on the batched device calls."""
     conns = router.conns
     route = np.frombuffer(route_b, dtype=L.ROUTE)
     cls, rconn = route["cls"], route["conn"]
@@ -713,6 +749,10 @@ def _routed_finish(router, datagrams: list, slots, uspaces, sexp, route_b, walke
     for k, f in enumerate(closed):
         if f and conns[k] is not None:
             conns[k].closed = True
+    if device_keys:
+        # _update_key_cached for all of them: the send directions from one device call
+        update_keys_batch(rolled, "remote_update", slots)
+        rolled = ()
     for pair in rolled:
         # both directions, as _update_key does; the receive one adopts the
         # cached context, whose slot then is the current one as it stands
@@ -720,7 +760,7 @@ def _routed_finish(router, datagrams: list, slots, uspaces, sexp, route_b, walke
     if deferred:
         # key-phase flips and numbers decoded under a stale expected number:
         # the general walk takes them in order from the state left above
-        rb = ReceiveBatch(slots=slots)
+        rb = ReceiveBatch(slots=slots, device_keys=device_keys)
         at = idx.tolist()
         for j in deferred:
             conn = conns[rconn[at[j]]]

@@ -159,6 +159,19 @@ typedef struct qpp_initial {
     uint8_t cid[20];
 } qpp_initial;             /* 32 bytes */
 
+/* One context's current traffic secret for the batched next_key_phase
+ * (qpp_keytab_derive_next): what a key update derives from, the
+ * header-protection key it keeps, and where the next phase goes. */
+typedef struct qpp_next_phase {
+    uint32_t slot;        /* slot to install the next phase in, or QPP_SLOT_NONE: derive and return only */
+    uint8_t  suite;
+    uint8_t  key_phase;   /* the NEXT phase's bit (the caller flips it) */
+    uint8_t  flags;       /* QPP_DERIVE_V2 */
+    uint8_t  secret_len;  /* 1..64, as qpp_secret */
+    uint8_t  secret[64];  /* the CURRENT phase's traffic secret */
+    uint8_t  hp[32];      /* the current header-protection key, kept */
+} qpp_next_phase;         /* 104 bytes */
+
 typedef struct qpp_keytab qpp_keytab;   /* device-resident expanded keys */
 typedef struct qpp_session qpp_session; /* pinned staging + device buffers + stream */
 
@@ -256,11 +269,39 @@ int qpp_keytab_derive_initial(qpp_keytab *kt, const qpp_initial *ini, uint32_t n
 int qpp_keytab_derive_initial_device(qpp_keytab *kt, const qpp_initial *d_ini, uint32_t n,
                                      const uint32_t *h_slots, qpp_key_material *d_km, uint8_t *d_secrets,
                                      void *stream);
-/* Where a qpp_keytab_derive_initial call's device time goes (diagnostic, for
- * tools/bench_initial_keys.py): enable != 0 makes the table's following calls
- * put timing events around their two kernels (0 off, -1 unchanged); derive_ms
- * and setup_ms (may be NULL) receive the last timed call's durations of the
- * derivation kernel and of the slot expansion (0 before any). */
+/* Batched next_key_phase (quic/crypto.py:148-168) for n contexts at once: the
+ * keys a key update moves to, derived from the current traffic secrets on the
+ * device, one lane per record, in one launch:
+ *     secret' = HKDF-Expand-Label(secret, "quic ku", "", hl)   hl = 48 for QPP_AES_256_GCM
+ *                                                              (SHA-384), else 32 (SHA-256);
+ *                                                              "quic ku" with QPP_DERIVE_V2 too
+ *     key(klen) / iv(12) of secret' with the "quic " labels, or the "quicv2 " ones
+ *                                                              with QPP_DERIVE_V2
+ *     hp      = the record's first klen bytes: a key update keeps the
+ *               header-protection key (deriving "quic hp" from secret', as
+ *               qpp_keytab_derive with updates = 1 does, gives the wrong key)
+ * Each record whose slot is not QPP_SLOT_NONE is then installed with the same
+ * slot expansion as qpp_keytab_set, under the record's key_phase.  km_out
+ * (host memory, may be NULL) receives n records, key and hp zero past klen; a
+ * record given QPP_SLOT_NONE is derived and returned all the same, with slot =
+ * QPP_SLOT_NONE, only not installed (the send direction of a key update).
+ * secrets_out (host memory, may be NULL) receives n x 64 bytes: secret', zero
+ * past hl (CryptoContext.secret of the next phase).
+ * QPP_E_ARG, with nothing launched, noted or installed: NULL kt, NULL rec with
+ * n > 0, n > 2^24, a slot that is neither < capacity nor QPP_SLOT_NONE, a
+ * suite above QPP_CHACHA20_POLY1305, secret_len outside 1..64, key_phase > 1,
+ * a flag bit other than QPP_DERIVE_V2.  The same slot named by two records is
+ * the caller's race, as with qpp_keytab_set.  n == 0 returns QPP_OK.
+ * Synchronous, like qpp_keytab_derive: the records are caller memory. */
+int qpp_keytab_derive_next(qpp_keytab *kt, const qpp_next_phase *rec, uint32_t n,
+                           qpp_key_material *km_out, uint8_t *secrets_out, void *stream);
+/* Where the device time of a qpp_keytab_derive_initial or
+ * qpp_keytab_derive_next call goes (diagnostic, for
+ * tools/bench_initial_keys.py and tools/bench_next_keys.py): enable != 0 makes
+ * the table's following calls put timing events around their two kernels (0
+ * off, -1 unchanged); derive_ms and setup_ms (may be NULL) receive the last
+ * timed call's durations of the derivation kernel and of the slot expansion
+ * (0 before any). */
 int qpp_keytab_derive_trace(qpp_keytab *kt, int enable, float *derive_ms, float *setup_ms);
 
 /* Batched packet protection on device buffers (asynchronous on `stream`).
