@@ -259,6 +259,33 @@ class PacketEngine:
         _crypto.route_phase(self.table, 0 if route is None else _ptr(route), _ptr(next_slots), int(n_next),
                             _ptr(desc), int(n), _ptr(inbuf), _ptr(phase), self._stream(stream))
 
+    def send_fill(self, send_conns, n_conn: int, offs, lens, conns, seqs, n: int, buf, desc, rec, buf_len=None,
+                  stream=None) -> None:
+        """qpp_send_fill on device buffers, before protect() of `desc` on the
+        same stream with `buf` as its input: the 1-RTT short header, packet
+        number and sample padding of n payloads that lie in `buf` at `offs`
+        (uint64) with `lens` (uint32), from the SEND_CONN array `send_conns`
+        indexed by `conns` (uint32) and each payload's ordinal among its
+        connection's, `seqs` (uint32).  Writes DESC records (`desc`) and
+        SEND_REC records (`rec`).  The caller keeps the regions [off -
+        SEND_HEAD, off + len + SEND_TAIL) pairwise disjoint; `buf_len`
+        defaults to the whole of `buf`."""
+        if buf_len is None:
+            buf_len = buf.numel() * buf.element_size()
+        _crypto.send_fill(self.table, _ptr(send_conns), int(n_conn), _ptr(offs), _ptr(lens), _ptr(conns),
+                          _ptr(seqs), int(n), _ptr(buf), int(buf_len), _ptr(desc), _ptr(rec), self._stream(stream))
+
+    def send_protect_host(self, send_conns, offs, lens, conns, seqs, data, out_len: int):
+        """Build headers and seal a host buffer of staged payloads in one call
+        (qpp_session_send_protect).  Returns (out, desc, records, results)."""
+        out, desc, rec, res = _crypto.send_protect_host(
+            self.table, np.ascontiguousarray(send_conns, dtype=L.SEND_CONN).tobytes(),
+            np.ascontiguousarray(offs, dtype=np.uint64).tobytes(), np.ascontiguousarray(lens, dtype=np.uint32).tobytes(),
+            np.ascontiguousarray(conns, dtype=np.uint32).tobytes(),
+            np.ascontiguousarray(seqs, dtype=np.uint32).tobytes(), bytes(data), int(out_len))
+        return (np.frombuffer(out, dtype=np.uint8), np.frombuffer(desc, dtype=L.DESC),
+                np.frombuffer(rec, dtype=L.SEND_REC), np.frombuffer(res, dtype=L.RESULT))
+
     def route_phase_unprotect_host(self, cid_map, cid_len: int, offs, lens, data, long_idx, conn_slot,
                                    conn_expected, conn_next, out_len: int, flags: int = 0):
         """route_walk_unprotect_host with the peers' key updates resolved on

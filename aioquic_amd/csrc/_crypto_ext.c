@@ -1796,6 +1796,196 @@ done:
     return ret;
 }
 
+/* ---- routed send: headers and packet numbers built on the device ---- */
+
+/* send_fill(table, sendconn_ptr, n_conn, off_ptr, len_ptr, conn_ptr, seq_ptr, n, buf_ptr, buf_len, desc_ptr,
+ *           rec_ptr, stream) */
+static PyObject *py_send_fill(PyObject *m, PyObject *args)
+{
+    PyObject *t;
+    unsigned long long cp, op, lp, ip, qp, bp, buf_len, dp, rp, sp;
+    unsigned int n_conn, n;
+    if (!PyArg_ParseTuple(args, "OKIKKKKIKKKKK", &t, &cp, &n_conn, &op, &lp, &ip, &qp, &n, &bp, &buf_len, &dp, &rp,
+                          &sp))
+        return NULL;
+    qpp_keytab *kt = as_table(t);
+    if (!kt) return NULL;
+    int rc = qpp_send_fill(kt, as_ptr(cp), n_conn, as_ptr(op), as_ptr(lp), as_ptr(ip), as_ptr(qp), n, as_ptr(bp),
+                           buf_len, as_ptr(dp), as_ptr(rp), as_ptr(sp));
+    if (rc == QPP_E_ARG) {
+        PyErr_SetString(PyExc_ValueError, "bad send_fill arguments (a null buffer)");
+        return NULL;
+    }
+    if (check_rc(rc) < 0) return NULL;
+    Py_RETURN_NONE;
+}
+
+static PyObject *py_send_launches(PyObject *m, PyObject *unused)
+{
+    return PyLong_FromUnsignedLongLong(qpp_send_launches());
+}
+
+static const char *const k_send_refused =
+    "bad send arguments (offsets not strictly increasing, a packet's region overlapping its predecessor's or outside "
+    "the input or the output buffer, a connection index out of range, or a slot outside the table); nothing was "
+    "launched";
+
+/* send_protect_host(table, sendconn, off_u64, len_u32, conn_u32, seq_u32, data, out_len)
+ *     -> (out, desc, records, results)
+ * qpp_session_send_protect over the caller's own arrays and staged buffer. */
+static PyObject *py_send_protect_host(PyObject *m, PyObject *args)
+{
+    PyObject *t;
+    const char *sc, *offs, *lens, *conns, *seqs, *data;
+    Py_ssize_t l_sc, l_offs, l_lens, l_conns, l_seqs, l_data, out_len;
+    if (!PyArg_ParseTuple(args, "Oy#y#y#y#y#y#n", &t, &sc, &l_sc, &offs, &l_offs, &lens, &l_lens, &conns, &l_conns,
+                          &seqs, &l_seqs, &data, &l_data, &out_len))
+        return NULL;
+    qpp_keytab *kt = as_table(t);
+    if (!kt) return NULL;
+    const Py_ssize_t n = l_lens / 4, nc = l_sc / (Py_ssize_t)sizeof(qpp_send_conn);
+    if (check_len(l_sc, nc, sizeof(qpp_send_conn), "sendconn") < 0 || check_len(l_offs, n, 8, "off") < 0 ||
+        check_len(l_lens, n, 4, "len") < 0 || check_len(l_conns, n, 4, "conn") < 0 ||
+        check_len(l_seqs, n, 4, "seq") < 0)
+        return NULL;
+    if (out_len < 0 || n > 0x7fffffff || nc > 0x7fffffff) {
+        PyErr_SetString(PyExc_ValueError, "bad array lengths or output length");
+        return NULL;
+    }
+    const Py_ssize_t size[4] = {out_len, n * (Py_ssize_t)sizeof(qpp_desc), n * (Py_ssize_t)sizeof(qpp_send_rec),
+                                n * (Py_ssize_t)sizeof(qpp_result)};
+    char *b[4] = {NULL};
+    PyObject *ret = PyTuple_New(4);
+    for (Py_ssize_t k = 0; ret && k < 4; ++k) {
+        PyObject *o = PyBytes_FromStringAndSize(NULL, size[k]);
+        if (!o || PyTuple_SetItem(ret, k, o) < 0) Py_CLEAR(ret);
+        else b[k] = PyBytes_AsString(o);
+    }
+    qpp_session *s = ret ? session() : NULL;
+    if (!s) {
+        Py_XDECREF(ret);
+        return NULL;
+    }
+    memset(b[0], 0, (size_t)size[0]);  /* an empty batch leaves `out` as zeros */
+    int rc;
+    Py_BEGIN_ALLOW_THREADS
+    rc = qpp_session_send_protect(s, kt, (const qpp_send_conn *)sc, (uint32_t)nc, (const uint64_t *)offs,
+                                  (const uint32_t *)lens, (const uint32_t *)conns, (const uint32_t *)seqs, (uint32_t)n,
+                                  (const uint8_t *)data, (size_t)l_data, (uint8_t *)b[0], (size_t)out_len,
+                                  (qpp_desc *)b[1], (qpp_send_rec *)b[2], (qpp_result *)b[3]);
+    Py_END_ALLOW_THREADS
+    if (rc == QPP_E_ARG) PyErr_SetString(PyExc_ValueError, k_send_refused);
+    if (rc == QPP_E_ARG || check_rc(rc) < 0) Py_CLEAR(ret);
+    return ret;
+}
+
+/* send_routed(table, sendconn, conn_u32, payloads) -> (datagrams, records, results)
+ * The batched sender without a host header pass: payload k (bytes) of
+ * connection conn[k] is staged into the session's pinned input at an offset
+ * computed here, QPP_SEND_HEAD bytes before it and QPP_SEND_TAIL after it
+ * free; its ordinal among its connection's payloads is counted in the same
+ * pass; qpp_session_send_protect builds the headers, numbers and padding and
+ * seals the packets.  Each datagram comes back as one bytes object cut from
+ * the pinned output (b"" for a packet whose record or result is not OK). */
+static PyObject *py_send_routed(PyObject *m, PyObject *args)
+{
+    PyObject *t, *payloads;
+    const char *a_sc, *a_conn;
+    Py_ssize_t l_sc, l_conn;
+    if (!PyArg_ParseTuple(args, "Oy#y#O!", &t, &a_sc, &l_sc, &a_conn, &l_conn, &PyList_Type, &payloads)) return NULL;
+    qpp_keytab *kt = as_table(t);
+    if (!kt) return NULL;
+    const Py_ssize_t n = l_conn / 4, nc = l_sc / (Py_ssize_t)sizeof(qpp_send_conn);
+    if (check_len(l_sc, nc, sizeof(qpp_send_conn), "sendconn") < 0 || check_len(l_conn, n, 4, "conn") < 0) return NULL;
+    /* a snapshot holding a reference to every payload: the copies below run
+       without the GIL, while another thread may change the caller's list */
+    payloads = PySequence_Tuple(payloads);
+    if (!payloads) return NULL;
+    PyObject *ret = NULL, *wires = NULL, *rec = NULL, *res = NULL;
+    Scratch sc = {{NULL}, 0, 0};
+    if (PyTuple_Size(payloads) != n || n > 0x7fffffff || nc > 0x7fffffff) {
+        PyErr_SetString(PyExc_ValueError, "one connection index per payload");
+        goto done;
+    }
+    uint64_t *off = SCRATCH(&sc, uint64_t, n + 1);
+    uint32_t *len = SCRATCH(&sc, uint32_t, n + 1);
+    uint32_t *seq = SCRATCH(&sc, uint32_t, n + 1);
+    uint32_t *count = SCRATCH0(&sc, uint32_t, nc + 1);
+    uint8_t **cd = SCRATCH(&sc, uint8_t *, n + 1);
+    const uint8_t **cs = SCRATCH(&sc, const uint8_t *, n + 1);
+    size_t *cl = SCRATCH(&sc, size_t, n + 1);
+    rec = PyBytes_FromStringAndSize(NULL, n * (Py_ssize_t)sizeof(qpp_send_rec));
+    res = PyBytes_FromStringAndSize(NULL, n * (Py_ssize_t)sizeof(qpp_result));
+    if (sc.failed || !rec || !res) {
+        PyErr_NoMemory();
+        goto done;
+    }
+    const uint32_t *conn = (const uint32_t *)a_conn;
+    size_t total = 0, bytes = 0;
+    for (Py_ssize_t k = 0; k < n; ++k) {
+        PyObject *o = PyTuple_GetItem(payloads, k);
+        if (!PyBytes_Check(o) || PyBytes_Size(o) > QPP_PACKET_MAX) {
+            PyErr_SetString(PyExc_TypeError, "payloads must be bytes of at most 1500");
+            goto done;
+        }
+        len[k] = (uint32_t)PyBytes_Size(o);
+        off[k] = total + QPP_SEND_HEAD;
+        total = (size_t)off[k] + len[k] + QPP_SEND_TAIL;
+        bytes += len[k];
+        /* (an index out of range is refused by the session's check below) */
+        seq[k] = conn[k] < (uint32_t)nc ? count[conn[k]]++ : 0;
+    }
+    {
+        qpp_session *s = session();
+        uint8_t *hin, *hout;
+        if (!s || check_rc(qpp_session_stage(s, total ? total : 1, (uint32_t)(n ? n : 1), &hin, &hout)) < 0) goto done;
+        for (Py_ssize_t k = 0; k < n; ++k) {
+            cd[k] = hin + off[k];
+            cs[k] = (const uint8_t *)PyBytes_AsString(PyTuple_GetItem(payloads, k));
+            cl[k] = len[k];
+        }
+        qpp_send_rec *rr = (qpp_send_rec *)PyBytes_AsString(rec);
+        qpp_result *rs = (qpp_result *)PyBytes_AsString(res);
+        int rc;
+        Py_BEGIN_ALLOW_THREADS  /* the snapshot holds every payload */
+        par_copy(cd, cs, cl, (size_t)n, bytes);
+        rc = qpp_session_send_protect(s, kt, (const qpp_send_conn *)a_sc, (uint32_t)nc, off, len, conn, seq,
+                                      (uint32_t)n, hin, total, hout, total, NULL, rr, rs);
+        Py_END_ALLOW_THREADS
+        if (rc == QPP_E_ARG) PyErr_SetString(PyExc_ValueError, k_send_refused);
+        if (rc == QPP_E_ARG || check_rc(rc) < 0) goto done;
+        wires = PyList_New(n);
+        bytes = 0;
+        for (Py_ssize_t k = 0; wires && k < n; ++k) {
+            const int ok = rr[k].status == QPP_SN_OK && rs[k].status == QPP_S_OK;
+            cl[k] = ok ? rs[k].out_len : 0;
+            /* allocated here, filled below without the GIL (not yet shared) */
+            PyObject *o = PyBytes_FromStringAndSize(NULL, (Py_ssize_t)cl[k]);
+            if (!o) {
+                Py_CLEAR(wires);
+                break;
+            }
+            PyList_SetItem(wires, k, o);
+            cd[k] = (uint8_t *)PyBytes_AsString(o);
+            cs[k] = hout + off[k] - rr[k].hdr_len;
+            bytes += cl[k];
+        }
+        if (wires) {
+            Py_BEGIN_ALLOW_THREADS
+            par_copy(cd, cs, cl, (size_t)n, bytes);
+            Py_END_ALLOW_THREADS
+            ret = PyTuple_Pack(3, wires, rec, res);
+        }
+    }
+done:
+    Py_XDECREF(wires);
+    Py_XDECREF(rec);
+    Py_XDECREF(res);
+    Py_DECREF(payloads);
+    scratch_free_all(&sc);
+    return ret;
+}
+
 /* receive_short's slot_of: closed on entry / no receive key (no launch) */
 #define RS_CLOSED 0xfffffffeu
 
@@ -3005,6 +3195,11 @@ static PyMethodDef module_methods[] = {
     {"route_accept", py_route_accept, METH_VARARGS, "qpp_route_accept on device buffers"},
     {"route_phase", py_route_phase, METH_VARARGS, "qpp_route_phase on device buffers"},
     {"route_phase_launches", py_route_phase_launches, METH_NOARGS, "qpp_route_phase_launches()"},
+    {"send_fill", py_send_fill, METH_VARARGS, "qpp_send_fill on device buffers"},
+    {"send_launches", py_send_launches, METH_NOARGS, "qpp_send_launches()"},
+    {"send_protect_host", py_send_protect_host, METH_VARARGS, "qpp_session_send_protect on host arrays"},
+    {"send_routed", py_send_routed, METH_VARARGS,
+     "stage payloads, build their 1-RTT headers on the device and seal them: one bytes per datagram"},
     {"route_phase_unprotect_host", py_route_phase_unprotect_host, METH_VARARGS,
      "qpp_session_route_phase_unprotect: route, walk, resolve key phases and unprotect host buffers in one call"},
     {"receive_routed_phase", py_receive_routed_phase, METH_VARARGS,

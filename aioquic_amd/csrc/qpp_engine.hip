@@ -30,6 +30,7 @@
 #include "qpp_next.h"
 #include "qpp_internal.h"
 #include "qpp_phase.h"
+#include "qpp_send.h"
 
 namespace qpp {
 
@@ -2553,6 +2554,47 @@ __global__ __launch_bounds__(kMaskWG) void k_phase(const KeySlot *__restrict__ s
     phase[i] = flip;
 }
 
+// The send side's counterpart of k_route (qpp_send_fill, qpp_send.h): one lane
+// per payload writes its 1-RTT short header, packet number, sample padding,
+// protect descriptor and record, from its connection's entry of the send-state
+// array.  No LDS, no atomics, no cross-lane ranking (the host counted seq);
+// plain vector stores.  desc[i] and rec[i] are written whole by every lane; the
+// buffer only by a lane qpp_sn::decide passed, and only inside its own region.
+// A lane reads no byte of the buffer.
+constexpr int kSendWG = 256;
+__global__ __launch_bounds__(kSendWG) void k_send(const KeySlot *__restrict__ slots, uint32_t cap,
+                                                  const qpp_send_conn *__restrict__ conns, uint32_t n_conn,
+                                                  const uint64_t *__restrict__ off, const uint32_t *__restrict__ len,
+                                                  const uint32_t *__restrict__ conn, const uint32_t *__restrict__ seq,
+                                                  uint32_t n, uint8_t *__restrict__ buf, uint64_t buf_len,
+                                                  qpp_desc *__restrict__ desc, qpp_send_rec *__restrict__ rec)
+{
+    static_assert(sizeof(qpp_send_conn) == sizeof(qpp_sn::Conn) && sizeof(qpp_send_rec) == sizeof(qpp_sn::Rec) &&
+                      sizeof(qpp_desc) == sizeof(qpp_sn::Desc) && QPP_SEND_PN_LEN == qpp_sn::kPnLen &&
+                      QPP_SEND_HEAD == qpp_sn::kHead && QPP_SEND_TAIL == qpp_sn::kTail &&
+                      QPP_SN_OK == qpp_sn::kOk && QPP_SN_CONN == qpp_sn::kConn && QPP_SN_CID == qpp_sn::kCid &&
+                      QPP_SN_NO_KEY == qpp_sn::kNoKey && QPP_SN_EMPTY == qpp_sn::kEmpty &&
+                      QPP_SN_PN == qpp_sn::kPn && QPP_SN_ROOM == qpp_sn::kRoom &&
+                      QPP_SLOT_NONE == qpp_sn::kSlotNone && QPP_CID_MAX == qpp_sn::kCidMax &&
+                      QPP_TAG_LEN == qpp_sn::kTag && QPP_CHACHA20_POLY1305 == qpp_sn::kSuiteMax,
+                  "qpp_send.h restates the ABI records");
+    const uint32_t i = blockIdx.x * kSendWG + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t ci = conn[i];
+    const bool conn_ok = ci < n_conn;
+    qpp_sn::Conn c = {};
+    qpp_sn::Slot s = {qpp_sn::kSuiteEmpty, 0};
+    if (conn_ok) {
+        __builtin_memcpy(&c, conns + ci, sizeof(c));
+        if (c.slot < cap) s = qpp_sn::Slot{slots[c.slot].suite, slots[c.slot].key_phase};
+    }
+    const uint64_t o = off[i];
+    const uint32_t l = len[i];
+    const qpp_sn::Plan p = qpp_sn::decide(conn_ok, c, s, o, l, seq[i], buf_len);
+    qpp_sn::emit(p, c, o, l, buf, reinterpret_cast<qpp_sn::Desc *>(desc + i),
+                 reinterpret_cast<qpp_sn::Rec *>(rec + i));
+}
+
 // --------------------------------------------------------------- key setup --
 
 // FIPS-197 sec. 5.2 in little-endian words (RotWord = rotr 8, Rcon in byte 0).
@@ -3614,6 +3656,25 @@ int qpp_route_phase(const qpp_keytab *kt, const qpp_route_rec *d_route, const ui
 }
 
 uint64_t qpp_route_phase_launches(void) { return g_phase_launches.load(std::memory_order_relaxed); }
+
+static std::atomic<uint64_t> g_send_launches{0};
+
+int qpp_send_fill(const qpp_keytab *kt, const qpp_send_conn *d_sendconn, uint32_t n_conn, const uint64_t *d_off,
+                  const uint32_t *d_len, const uint32_t *d_conn, const uint32_t *d_seq, uint32_t n, uint8_t *d_buf,
+                  uint64_t buf_len, qpp_desc *d_desc, qpp_send_rec *d_rec, void *stream)
+{
+    if (!kt) return QPP_E_ARG;
+    if (n == 0) return QPP_OK;
+    if (!d_off || !d_len || !d_conn || !d_seq || !d_buf || !d_desc || !d_rec || (n_conn && !d_sendconn))
+        return QPP_E_ARG;
+    hipLaunchKernelGGL(k_send, dim3((n + kSendWG - 1) / kSendWG), dim3(kSendWG), 0, (hipStream_t)stream, kt->d_slots,
+                       kt->cap, d_sendconn, n_conn, d_off, d_len, d_conn, d_seq, n, d_buf, buf_len, d_desc, d_rec);
+    HIPCHK(hipGetLastError());
+    g_send_launches.fetch_add(1, std::memory_order_relaxed);
+    return QPP_OK;
+}
+
+uint64_t qpp_send_launches(void) { return g_send_launches.load(std::memory_order_relaxed); }
 
 int qpp_internal_launch_xfer(uint8_t *d0, const uint8_t *s0, size_t n0, uint8_t *d1, const uint8_t *s1, size_t n1,
                              hipStream_t st)

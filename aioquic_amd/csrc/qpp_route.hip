@@ -24,6 +24,7 @@
 #include "qpp_accept.h"
 #include "qpp_reply.h"
 #include "qpp_route.h"
+#include "qpp_send.h"
 #include "qpp_token.h"
 #include "qpp_walk.h"
 
@@ -1161,6 +1162,70 @@ int qpp_session_serve_unprotect(qpp_session *s, qpp_keytab *kt, const qpp_cidmap
     return settle(s, route_unprotect(s, kt, m, cid_len, off, len, n, in, in_len, true, long_idx, n_long, conn_slot,
                                      conn_expected, n_conn, desc_flags, out, out_len, desc_out, route_out, res,
                                      walk_out, walk_n_out, &ac, NULL, NULL, &rp, &tk));
+}
+
+// qpp_send_fill + qpp_protect on host buffers: the payloads staged at their
+// offsets go up with [off | len | conn | seq | sendconn] in the session's own
+// scratch, k_send writes headers and padding into the device input, one
+// unplanned protect runs from it to the device output at the same offsets, and
+// the output comes back with [desc | rec | results].
+static int send_protect(qpp_session *s, const qpp_keytab *kt, const qpp_send_conn *sendconn, uint32_t n_conn,
+                        const uint64_t *off, const uint32_t *len, const uint32_t *conn, const uint32_t *seq,
+                        uint32_t n, const uint8_t *in, size_t in_len, uint8_t *out, size_t out_len,
+                        qpp_desc *desc_out, qpp_send_rec *rec_out, qpp_result *res)
+{
+    if (!s || !kt) return QPP_E_ARG;
+    if (n == 0) return QPP_OK;
+    if (!off || !len || !conn || !seq || !in || !out || !rec_out || !res || (n_conn && !sendconn)) return QPP_E_ARG;
+    static_assert(sizeof(qpp_send_conn) == sizeof(qpp_sn::Conn), "ABI record");
+    if (!qpp_sn::batch_ok(reinterpret_cast<const qpp_sn::Conn *>(sendconn), n_conn, qpp_keytab_capacity(kt), off, len,
+                          conn, n, in_len, out_len))
+        return QPP_E_ARG;
+    const size_t o_len = al256((size_t)n * 8), o_conn = o_len + al256((size_t)n * 4),
+                 o_seq = o_conn + al256((size_t)n * 4), o_sc = o_seq + al256((size_t)n * 4),
+                 up = o_sc + al256((size_t)n_conn * sizeof(qpp_send_conn));
+    const size_t o_rec = al256((size_t)n * sizeof(qpp_desc)), o_res = o_rec + al256((size_t)n * sizeof(qpp_send_rec)),
+                 down = o_res + al256((size_t)n * sizeof(qpp_result));
+    qpp_session_bufs b;
+    int rc = qpp_internal_session_bufs(s, in_len > out_len ? in_len : out_len, n, up + down, &b);
+    if (rc != QPP_OK) return rc;
+    uint8_t *hu = b.h_scratch, *du = b.d_scratch, *hd = b.h_scratch + up, *dd = b.d_scratch + up;
+    memcpy(hu, off, (size_t)n * 8);
+    memcpy(hu + o_len, len, (size_t)n * 4);
+    memcpy(hu + o_conn, conn, (size_t)n * 4);
+    memcpy(hu + o_seq, seq, (size_t)n * 4);
+    if (n_conn) memcpy(hu + o_sc, sendconn, (size_t)n_conn * sizeof(qpp_send_conn));
+    if (in != b.h_in) memcpy(b.h_in, in, in_len);  // staged by the caller already?
+    HIPCHK(hipMemcpyAsync(du, hu, up, hipMemcpyHostToDevice, b.stream));
+    HIPCHK(hipMemcpyAsync(b.d_in, b.h_in, in_len, hipMemcpyHostToDevice, b.stream));
+    // bytes no packet writes (the gaps between the regions) come back as zeros
+    HIPCHK(hipMemsetAsync(b.d_out, 0, out_len, b.stream));
+    qpp_desc *d_desc = (qpp_desc *)dd;
+    qpp_send_rec *d_rec = (qpp_send_rec *)(dd + o_rec);
+    qpp_result *d_res = (qpp_result *)(dd + o_res);
+    rc = qpp_send_fill(kt, (const qpp_send_conn *)(du + o_sc), n_conn, (const uint64_t *)du,
+                       (const uint32_t *)(du + o_len), (const uint32_t *)(du + o_conn),
+                       (const uint32_t *)(du + o_seq), n, b.d_in, in_len, d_desc, d_rec, b.stream);
+    if (rc != QPP_OK) return rc;
+    rc = qpp_protect(kt, d_desc, n, b.d_in, b.d_out, d_res, b.stream);
+    if (rc != QPP_OK) return rc;
+    HIPCHK(hipMemcpyAsync(b.h_out, b.d_out, out_len, hipMemcpyDeviceToHost, b.stream));
+    HIPCHK(hipMemcpyAsync(hd, dd, down, hipMemcpyDeviceToHost, b.stream));
+    HIPCHK(hipStreamSynchronize(b.stream));
+    if (out != b.h_out) memcpy(out, b.h_out, out_len);
+    if (desc_out) memcpy(desc_out, hd, (size_t)n * sizeof(qpp_desc));
+    memcpy(rec_out, hd + o_rec, (size_t)n * sizeof(qpp_send_rec));
+    memcpy(res, hd + o_res, (size_t)n * sizeof(qpp_result));
+    return QPP_OK;
+}
+
+int qpp_session_send_protect(qpp_session *s, const qpp_keytab *kt, const qpp_send_conn *sendconn, uint32_t n_conn,
+                             const uint64_t *off, const uint32_t *len, const uint32_t *conn, const uint32_t *seq,
+                             uint32_t n, const uint8_t *in, size_t in_len, uint8_t *out, size_t out_len,
+                             qpp_desc *desc_out, qpp_send_rec *rec_out, qpp_result *res)
+{
+    return settle(s, send_protect(s, kt, sendconn, n_conn, off, len, conn, seq, n, in, in_len, out, out_len, desc_out,
+                                  rec_out, res));
 }
 
 }  // extern "C"

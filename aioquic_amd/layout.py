@@ -139,6 +139,19 @@ TOKEN_REC = np.dtype([("status", "u1"), ("odcid_len", "u1"), ("rscid_len", "u1")
 TOKEN_STRIDE, TOKEN_MIN, TOKEN_MAX = 128, 27, 128
 ACC_BAD_TOKEN = 7
 TK_OK, TK_NONE, TK_LENGTH, TK_BOUNDS, TK_AUTH, TK_FORM, TK_ADDR = 0, 1, 2, 3, 4, 5, 6
+# routed send (qpp_send_fill): SEND_CONN is one connection's send state (its
+# next packet number, 1-RTT send slot, the peer's CID and the spin bit),
+# SEND_REC what the device built for one payload (an SN_* status, the first
+# failing check).  A payload at `off` may have SEND_HEAD bytes written before
+# it and SEND_TAIL behind it: the longest header; the largest padding + the tag
+SEND_CONN = np.dtype([("next_pn", "<u8"), ("slot", "<u4"), ("cid_len", "u1"), ("spin", "u1"), ("cid", "u1", (20,)),
+                      ("rsv", "u1", (6,))])
+SEND_REC = np.dtype([("pn", "<u8"), ("hdr_len", "<u2"), ("status", "u1"), ("rsv", "u1", (5,))])
+SEND_PN_LEN = 2                         # QPP_SEND_PN_LEN
+SEND_HEAD = 1 + CID_MAX + SEND_PN_LEN   # QPP_SEND_HEAD
+SEND_TAIL = 1 + TAG_LEN                 # QPP_SEND_TAIL
+SN_OK, SN_CONN, SN_CID, SN_NO_KEY, SN_EMPTY, SN_PN, SN_ROOM = 0, 1, 2, 3, 4, 5, 6
+assert SEND_CONN.itemsize == 40 and SEND_REC.itemsize == 16
 assert REPLY.itemsize == 8 and TOKEN_REC.itemsize == 48
 assert DESC.itemsize == 40 and RESULT.itemsize == 16 and KEY_MATERIAL.itemsize == 84
 assert WALK.itemsize == 24 and ACCEPT.itemsize == 8
@@ -202,6 +215,20 @@ def initial_record(slot_client: int, slot_server: int, cid: bytes, *, v2: bool =
     rec["slot_server"] = slot_server
     rec["cid_len"] = len(cid)
     rec["flags"] = DERIVE_V2 if v2 else 0
+    rec["cid"][0, : len(cid)] = np.frombuffer(cid, dtype=np.uint8)
+    return rec
+
+
+def send_conn(next_pn: int, slot: int, cid: bytes, spin: bool = False):
+    """One qpp_send_conn: a connection's next packet number, its 1-RTT send
+    slot (or SLOT_NONE), the peer's connection ID (0..20 bytes) and spin bit."""
+    if len(cid) > CID_MAX:
+        raise ValueError("connection ID longer than 20 bytes")
+    rec = np.zeros(1, dtype=SEND_CONN)
+    rec["next_pn"] = next_pn
+    rec["slot"] = slot
+    rec["cid_len"] = len(cid)
+    rec["spin"] = 1 if spin else 0
     rec["cid"][0, : len(cid)] = np.frombuffer(cid, dtype=np.uint8)
     return rec
 

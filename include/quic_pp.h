@@ -794,6 +794,72 @@ int qpp_route_phase(const qpp_keytab *kt, const qpp_route_rec *d_route /* may be
  * library loaded).  Diagnostic: a batch with no next-phase slot makes none. */
 uint64_t qpp_route_phase_launches(void);
 
+/* ---- routed send: 1-RTT headers and packet numbers built on the device ----
+ * The mirror of routed receive.  The caller holds its connections' send state
+ * in one device array, hands payloads and a connection index each, and a
+ * kernel in front of qpp_protect writes what the reference's builder writes
+ * per 1-RTT packet (quic/packet_builder.py:19-20 PACKET_NUMBER_SEND_SIZE,
+ * :264-296 _end_packet's sample padding, :330-339 its short header): the
+ * header, the packet number, the padding and an ordinary qpp_desc.  Long headers, datagram padding, frames and
+ * congestion accounting stay with the caller's builder. */
+#define QPP_SEND_PN_LEN 2                               /* packet_builder.py:20 PACKET_NUMBER_SEND_SIZE */
+#define QPP_SEND_HEAD (1 + QPP_CID_MAX + QPP_SEND_PN_LEN) /* the longest header: first byte, CID, number */
+#define QPP_SEND_TAIL (1 + QPP_TAG_LEN)                 /* the largest padding (a 1-byte payload's) + tag */
+#define QPP_SN_OK 0
+#define QPP_SN_CONN 1     /* p_conn[i] >= n_conn */
+#define QPP_SN_CID 2      /* the connection's cid_len > QPP_CID_MAX */
+#define QPP_SN_NO_KEY 3   /* the connection's slot is QPP_SLOT_NONE, past the table, or not installed */
+#define QPP_SN_EMPTY 4    /* len == 0: the builder cancels an empty packet (packet_builder.py:266,361-363) */
+#define QPP_SN_PN 5       /* next_pn + seq wraps or is >= 2^62 */
+#define QPP_SN_ROOM 6     /* p_off < hdr_len, or p_off + len + pad + QPP_TAG_LEN > buf_len */
+/* One connection's send state. */
+typedef struct qpp_send_conn {
+    uint64_t next_pn;  /* the packet number of the connection's first packet of the batch */
+    uint32_t slot;     /* its 1-RTT send key slot; the header's key-phase bit is the slot's own */
+    uint8_t cid_len;   /* the peer's connection ID, 0..QPP_CID_MAX bytes */
+    uint8_t spin;      /* the spin bit (nonzero: set) */
+    uint8_t cid[20];   /* zero padded */
+    uint8_t rsv[6];
+} qpp_send_conn;       /* 40 bytes */
+typedef struct qpp_send_rec {
+    uint64_t pn;       /* the packet's number; 0 unless status is QPP_SN_OK */
+    uint16_t hdr_len;  /* 1 + cid_len + QPP_SEND_PN_LEN; 0 unless status is QPP_SN_OK */
+    uint8_t status;    /* QPP_SN_*: the first failing check, in the order above */
+    uint8_t rsv[5];
+} qpp_send_rec;        /* 16 bytes */
+/* qpp_send_fill: asynchronous on `stream`; runs before qpp_protect on the same
+ * stream, over the same buffer.  Packet i's payload lies at d_buf[d_off[i],
+ * d_off[i] + d_len[i]) already and belongs to connection C = d_sendconn[
+ * d_conn[i]]; d_seq[i] is its ordinal among C's packets of this batch, counted
+ * by the caller (the device ranks nothing and uses no atomics).  One lane per
+ * packet.  With pn = C.next_pn + d_seq[i], hdr_len = 1 + C.cid_len +
+ * QPP_SEND_PN_LEN and pad = max(0, 4 - QPP_SEND_PN_LEN - len), lane i writes
+ *   d_buf[off - hdr_len]          0x40 | spin << 5 | key_phase << 2 | (QPP_SEND_PN_LEN - 1),
+ *                                 key_phase the installed slot C.slot's own (a local key
+ *                                 update is then only a new slot)
+ *   d_buf[off - hdr_len + 1 ..]   C.cid[0, cid_len), then pn & 0xffff big-endian
+ *   d_buf[off + len, + pad)       zeros: PADDING frames, so that the header-protection sample
+ *                                 exists (the descriptor's len includes them)
+ *   d_desc[i] = {in_off = out_off = off - hdr_len, len + pad, hdr_len, flags 0, pn, C.slot}
+ *   d_rec[i]  = {pn, hdr_len, QPP_SN_OK}
+ * A lane whose status is not QPP_SN_OK writes no byte of d_buf, the inert
+ * descriptor {in_off = out_off = off, len 0, hdr_len 0, QPP_SLOT_NONE} (which
+ * qpp_protect answers with QPP_S_NO_KEY, touching nothing) and a record with
+ * pn 0.  Descriptors and records are written whole for every lane, so the same
+ * input gives the same bytes.  A lane reads nothing of the payload.  Length
+ * limits beyond the buffer's (QPP_PACKET_MAX) stay with qpp_protect, as
+ * QPP_S_LENGTH.
+ * The caller's contract for the device form: the regions [d_off[i] -
+ * QPP_SEND_HEAD, d_off[i] + d_len[i] + QPP_SEND_TAIL) are pairwise disjoint;
+ * the lanes' stores and the protect's then never meet.
+ * QPP_E_ARG: NULL kt, or with n > 0 a NULL array or buffer, or a NULL
+ * d_sendconn with n_conn > 0.  n == 0 returns QPP_OK and launches nothing. */
+int qpp_send_fill(const qpp_keytab *kt, const qpp_send_conn *d_sendconn, uint32_t n_conn, const uint64_t *d_off,
+                  const uint32_t *d_len, const uint32_t *d_conn, const uint32_t *d_seq, uint32_t n, uint8_t *d_buf,
+                  uint64_t buf_len, qpp_desc *d_desc, qpp_send_rec *d_rec, void *stream);
+/* qpp_send_fill launches (process-wide, since the library loaded).  Diagnostic. */
+uint64_t qpp_send_launches(void);
+
 /* Header-protection masks: replaces HeaderProtection_mask (_crypto.c:278-287).
  * d_samples: n x 16 bytes, d_masks: n x 16 bytes (first 5 used). */
 int qpp_hp_mask(const qpp_keytab *kt, const uint32_t *d_slots, const uint8_t *d_samples,
@@ -973,6 +1039,28 @@ int qpp_session_serve_unprotect(qpp_session *s, qpp_keytab *kt, const qpp_cidmap
                                 qpp_walk_rec *walk_out, uint32_t *walk_n_out, qpp_accept_rec *acc_out,
                                 qpp_key_material *km_out, uint8_t *secrets_out, uint8_t *reply_out,
                                 qpp_reply_rec *reply_rec_out, qpp_token_rec *tokrec_out);
+/* qpp_send_fill + qpp_protect on host buffers, the send side's counterpart of
+ * qpp_session_route_unprotect: one H2D of the staged buffer `in` (the payloads
+ * at off[i], room for a header before and padding and tag after each) and of
+ * [off | len | conn | seq | sendconn], the filling kernel, one unplanned
+ * qpp_protect over the n descriptors from the session's input buffer to its
+ * output buffer at the same offsets, one D2H of the output and of [desc | rec |
+ * results] (desc_out may be NULL).  Serial form only.  Works with the
+ * session's own pinned staging (qpp_session_stage) as `in` / `out`.
+ * Checked on the host before anything is launched; a violation is QPP_E_ARG
+ * and nothing is touched:
+ *   - off strictly increasing;
+ *   - every region [off[i] - QPP_SEND_HEAD, off[i] + len[i] + QPP_SEND_TAIL)
+ *     inside both buffers and behind its predecessor's;
+ *   - every conn[i] < n_conn;
+ *   - every sendconn[c].slot inside the table, or QPP_SLOT_NONE.
+ * With n == 0 it returns QPP_OK and launches nothing.  Output bytes no packet
+ * writes are zeros.  A packet qpp_send_fill refuses (rec_out[i].status) has
+ * QPP_S_NO_KEY in res[i] and no byte written. */
+int qpp_session_send_protect(qpp_session *s, const qpp_keytab *kt, const qpp_send_conn *sendconn, uint32_t n_conn,
+                             const uint64_t *off, const uint32_t *len, const uint32_t *conn, const uint32_t *seq,
+                             uint32_t n, const uint8_t *in, size_t in_len, uint8_t *out, size_t out_len,
+                             qpp_desc *desc_out, qpp_send_rec *rec_out, qpp_result *res);
 /* The session's own pinned staging buffers, sized for at least `bytes` of
  * input and of output and n packets; valid until the next call on the
  * session.  A caller that assembles its input straight into *h_in and passes
